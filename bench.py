@@ -6,14 +6,19 @@ CIFAR-10 2-stage images/s; 3.40-4.15 k img/s on CPU over localhost gRPC,
 BASELINE.md).  Synthetic fp32 images, random-init weights of the reference
 architecture.  Precision: the reference's fp32 contract, computed as **fp32
 (bf16x3 split emulation, ~2^-16 relative per product, fp32 accumulation)**:
-every product is three bf16 MFMA terms (ops/cifar.py); the line reports the
-measured max|dprob| against fp32 torch on 4096 images (outside the timed
-region).  ``--precision bf16`` is the reduced-precision variant (extra keys).
+every product is three bf16 MFMA terms (ops/cifar.py); with ``--full`` the line
+reports the measured max|dprob| against fp32 torch on 16384 images (outside the
+timed region).  ``--precision bf16`` is the reduced-precision variant (extra keys).
 Every timed step runs the complete forward of both stages (conv stage +
 fc/softmax/argmax stage) on fresh launches; nothing is cached across steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, write the last step's results (``--dump-outputs``), print the line.
+Everything else described below (p50 latency, the precision and distributed
+correctness checks, the hop bandwidth, every extra key) runs with ``--full``.
 
 Placements (the stage cut is the reference's at every N: conv | fc1+fc2+softmax,
 ``cifar_model_parts.py:29-58``, an fp32 16 KiB/img hop):
@@ -68,6 +73,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=65536, help="images sourced per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else this bench measures or checks: p50 latency, "
+                         "the precision check against fp32 torch, the extra keys (bf16, GPT-2, Llama-3 8B, GPT-2 XL), "
+                         "and at N>1 the distributed correctness check, the hop bandwidth and the decode rings")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (probabilities and "
+                         "predictions) as float32 DIR/<name>.npy (N = 1, or N > 1 with --placement pp2)")
     ap.add_argument("--no_fill", action="store_true",
                     help="linear N>1: stage-1 GPUs only serve received microbatches (no own images)")
     ap.add_argument("--fill_rows", type=int, default=-1, help="linear N>1: own images per round on a stage-1 GPU "
@@ -102,6 +114,10 @@ def parse():
                     help="N>1 without a launcher: wall-clock limit of the self-launched job "
                          "(-1 = --time_budget_s + 240 s)")
     a = ap.parse_args()
+    if a.dump_outputs and a.gpus > 1 and a.placement != "pp2":
+        ap.error(f"--dump-outputs is not implemented for --placement {a.placement}")
+    if a.dump_outputs and a.model != "cifar10":
+        ap.error(f"--dump-outputs is not implemented for --model {a.model}")
     if a.verify_images < 0:
         a.verify_images = 256 if a.cpu else VERIFY_IMAGES
     if a.launch_timeout < 0:
@@ -192,8 +208,11 @@ def bench_colocated(args, info):
         pipe()
     t0 = sync_time(info)
     for _ in range(args.steps):
-        pipe()
+        res = pipe()
     t1 = sync_time(info)
+    args._outputs = {"probs": res.probs, "pred": res.pred}  # what the last timed step returned
+    if not args.full:
+        return t1 - t0, args.batch, float("nan"), "pp2-colocated"
     # p50 single-image pipeline latency (both stages, one graph replay)
     lat = ColocatedPipeline([s0, s1], 1)
     lat.x.copy_(torch.randn(lat.x.shape, device=dev, generator=g))
@@ -253,6 +272,8 @@ def bench_interleaved(args, info):
         step()
     drain()
     t1 = sync_time(info)
+    if not args.full:
+        return t1 - t0, mb * M, float("nan"), f"pp2-interleaved-a2a-x{N}"
     # latency: one image per peer through stage0 -> all-to-all -> stage1
     lx = torch.randn((N - 1, 3, 32, 32), device=dev, generator=g)
     ly = torch.empty((N - 1, bw), dtype=bdt, device=dev)
@@ -299,19 +320,28 @@ def bench_pp2(args, info):
         xs = [torch.randn((mb, 3, 32, 32), device=dev, generator=g) for _ in range(M)]
         nxt = SplitLink([make_link(2 * j + 1, dev) for j in range(n)])
 
-        def stream(steps):
+        def stream(steps, sink=None):
             run_gpipe(s0, steps * M, mb, None, nxt, source=lambda i: xs[i % M], depth=2)
     else:
         prev = SplitLink([make_link(2 * a, dev) for a in range(n)])
 
-        def stream(steps):
-            run_gpipe(s1, steps * M, mb, prev, None, depth=2)
+        def stream(steps, sink=None):
+            run_gpipe(s1, steps * M, mb, prev, None, sink=sink, depth=2)
+
+    last = {}  # --dump-outputs: the last timed step's microbatches on a stage-1 GPU (copies: the slots are reused)
+
+    def keep(i, y):
+        if i >= (args.steps - 1) * M:
+            last[i] = (y.probs.clone(), y.pred.clone())
 
     stream(args.warmup)
     t0 = sync_time(info)
-    stream(args.steps)
+    stream(args.steps, keep if args.dump_outputs else None)
     t1 = sync_time(info)
-    p50 = pp2_latency(args, info, s0, s1, back)
+    if last:
+        args._outputs = {f"probs_rank{r}": torch.cat([last[i][0] for i in sorted(last)]),
+                         f"pred_rank{r}": torch.cat([last[i][1] for i in sorted(last)])}
+    p50 = pp2_latency(args, info, s0, s1, back) if args.full else float("nan")
     fabric = "rccl" if dev.type == "cuda" else "gloo-cpu"
     return t1 - t0, n * mb * M / N, p50, f"pp2-{fabric}-{n}x{n}" + ("-bipartite" if n > 1 else "")
 
@@ -774,6 +804,23 @@ def precision_check(dev, precision: str, n_img: int = 4096) -> dict:
             "precision_check_images": n_img}
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path: str, arrays: dict, budget: int) -> None:
+    """Write each tensor as float32 ``path/<name>.npy``.  An array larger than
+    its share of ``budget`` bytes is cut to a fixed seeded sample of its rows
+    (in row order), the same rows in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        rows = (budget // max(1, len(arrays))) // max(1, 4 * t[0].numel())
+        if t.shape[0] > rows:
+            g = torch.Generator().manual_seed(0)
+            t = t[torch.randperm(t.shape[0], generator=g)[:rows].sort().values.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def main():
     args = parse()
     from distributed_neural_networks_amd.parallel import selflaunch
@@ -828,7 +875,9 @@ def main():
     value = total / el
     extra = {}
     phases["headline_s"] = round(time.perf_counter() - tp, 2)
-    if N == 1 and not args.no_extra and info.device.type == "cuda":
+    if args.dump_outputs and getattr(args, "_outputs", None):
+        dump_outputs(args.dump_outputs, args._outputs, DUMP_BYTES // max(1, N // 2))
+    if N == 1 and args.full and not args.no_extra and info.device.type == "cuda":
         tp = time.perf_counter()
         extra = extra_keys(args, info)
         phases["extras_s"] = round(time.perf_counter() - tp, 2)
@@ -850,12 +899,12 @@ def main():
                        "stage_cut": {1: f"conv|fc (reference split, {hop_kib} KiB/img hop)",
                                      2: f"conv+fc1|fc2 ({hop_kib // 8} KiB/img hop)"}[args._cut]},
         }
-        if info.device.type == "cuda" and args.precision == "fp32":
+        if args.full and info.device.type == "cuda" and args.precision == "fp32":
             tp = time.perf_counter()
             out.update(precision_check(info.device, args.precision, 16384))
             phases["precision_check_s"] = round(time.perf_counter() - tp, 2)
         out.update(extra)
-    if N > 1 and args.placement == "pp2" and args.verify_images > 0:
+    if N > 1 and args.full and args.placement == "pp2" and args.verify_images > 0:
         # the answer that crossed the hops, against fp32 torch (pp2_verify)
         tp = time.perf_counter()
         try:
@@ -869,7 +918,7 @@ def main():
             if out is not None:
                 out["dist_verify_error"] = f"{type(e).__name__}: {e}"[:200]
         phases["dist_verify_s"] = round(time.perf_counter() - tp, 2)
-    if N > 1 and args.placement == "pp2":
+    if N > 1 and args.full and args.placement == "pp2":
         tp = time.perf_counter()
         try:
             with Deadline(min(120.0, max(10.0, args.time_budget_s - elapsed_s() - EXTRAS_MARGIN_S)), out, "hop"):
@@ -882,7 +931,7 @@ def main():
             if out is not None:
                 out["hop_GBps_error"] = f"{type(e).__name__}: {e}"[:200]
         phases["hop_s"] = round(time.perf_counter() - tp, 2)
-    if N > 1 and not args.no_extra:
+    if N > 1 and args.full and not args.no_extra:
         multi_gpu_extras(args, info, out, phases)
     if out is not None:
         phases["total_s"] = round(elapsed_s(), 2)

@@ -268,7 +268,7 @@ def test_bench_pp2_schedule_cpu(n, launcher):
     keys of BASELINE configs 3-5 (decode rings with per-token p50).  N = 4
     runs as the driver launches it, ``python bench.py --gpus 4`` with no
     launcher: bench.py must spawn the 4 ranks itself."""
-    d = _bench_cpu(n, launcher=launcher)
+    d = _bench_cpu(n, "--full", launcher=launcher)
     assert d["n_gpus"] == n and d["value"] > 0 and d["metric"] == "images/sec CIFAR-10 2-stage"
     assert d["dtype"].startswith("fp32") and "schedule test" in d["dtype"] and d["scaling"] == "weak"
     assert d["config"]["stage_cut"] == "conv|fc (reference split, 16 KiB/img hop)"
@@ -309,7 +309,7 @@ def test_bench_verify_sees_a_bad_hop_cpu(monkeypatch):
     check corrupted (every 7th row negated) and the ring's prompts changed for
     one microbatch, the keys fall below 1."""
     monkeypatch.setitem(ENV, "DNN_TEST_CORRUPT_VERIFY", "1")
-    d = _bench_cpu(2, "--no_extra")
+    d = _bench_cpu(2, "--full", "--no_extra")
     assert d["dist_argmax_agreement_vs_fp32_torch"] < 1.0
     assert d["dist_max_abs_dprob"] > 1e-3
     port = free_port()
@@ -377,6 +377,31 @@ def test_bench_other_placements_cpu(placement, n, fill):
         assert d["config"]["parallelism"] == f"pp2-fc1cut-{plan['n0']}x{plan['n1']}+fill"
         assert d["config"]["global_batch"] == plan["n0"] * 16 + plan["n1"] * fill * 2
         assert d["config"]["receiver_fill_images_per_step"] == plan["n1"] * fill * 2
+
+
+def test_bench_plain_run_dumps_outputs_cpu(tmp_path):
+    """A plain run (no ``--full``) measures the headline only, and
+    ``--dump-outputs`` writes what the last timed step's stage-1 rank computed:
+    the fp32 model's probabilities and predictions of rank 0's seeded images."""
+    import numpy as np
+    from distributed_neural_networks_amd import checkpoint as ckpt
+    from distributed_neural_networks_amd.models.cifar import NeuralNetwork
+    d = _bench_cpu(2, "--dump-outputs", str(tmp_path / "out"))
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "images/s"
+    assert d["value"] == pytest.approx(16 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert d["p50_latency_ms"] is None
+    assert not [k for k in d if k.startswith(("dist_", "hop_", "fc1cut_", "gpt2", "llama3"))], sorted(d)
+    assert sorted(os.listdir(tmp_path / "out")) == ["pred_rank1.npy", "probs_rank1.npy"]
+    probs, pred = np.load(tmp_path / "out" / "probs_rank1.npy"), np.load(tmp_path / "out" / "pred_rank1.npy")
+    assert probs.dtype == np.float32 and probs.shape == (16, 10) and pred.dtype == np.float32 and pred.shape == (16,)
+    g = torch.Generator().manual_seed(1)  # bench_pp2: rank r draws its images from seed 1 + r
+    x = torch.cat([torch.randn((8, 3, 32, 32), generator=g) for _ in range(2)])
+    m = NeuralNetwork().eval()
+    m.load_state_dict(ckpt.random_stage_state_dict("cifar10", 0, 3, True, True, 0))
+    with torch.no_grad():
+        want = m(x)
+    assert np.abs(probs - want.numpy()).max() < 1e-5
+    assert (pred == probs.argmax(1)).all()
 
 
 @pytest.mark.parametrize("n", [4, 8])

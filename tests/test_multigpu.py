@@ -66,7 +66,7 @@ def test_bench_pp2_headline(n):
     The line must carry the distributed correctness keys at 1.0."""
     _need(n)
     d = _bench("--gpus", str(n), "--steps", "3", "--warmup", "1", "--batch", "8192", "--latency_iters", "5",
-               "--no_extra")
+               "--full", "--no_extra")
     assert d["n_gpus"] == n and d["value"] > 0 and d["metric"] == "images/sec CIFAR-10 2-stage"
     assert d["config"]["p2p"] == "native"
     assert d["config"]["stage_cut"] == REF_CUT
@@ -89,7 +89,7 @@ def test_bench_full_line(n):
     fc1-cut and the BASELINE config 3/4/5 decode rings over RCCL, each ring's
     greedy tokens equal to the same stages colocated on rank 0's GPU."""
     _need(n)
-    d = _bench("--gpus", str(n), "--steps", "5", "--warmup", "2", timeout=1100)
+    d = _bench("--gpus", str(n), "--steps", "5", "--warmup", "2", "--full", timeout=1100)
     assert d["n_gpus"] == n and d["config"]["p2p"] == "native" and d["config"]["stage_cut"] == REF_CUT
     assert "extras_error" not in d, d.get("extras_error")
     assert d["fc1cut_images_per_s"] > 0

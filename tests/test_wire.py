@@ -77,39 +77,52 @@ def test_large_message_roundtrip():
     assert codec.decode(b.tensor).shape == (300, 4096)
 
 
-REF_PB2 = "/root/reference/node_service_pb2.py"
-
-
-def _reference_descriptor():
-    """The reference's serialized FileDescriptorProto (node_service_pb2.py:27),
-    parsed as DATA: the bytes literal is read with ast.literal_eval (literals
-    only, nothing of the reference file is executed or imported)."""
-    import ast
+def _proto_file_tables():
+    """Messages and services of the package's ``wire/node_service.proto`` (the
+    schema as text; no protoc here), in the form ``test_descriptor_matches_proto_file_field_by_field``
+    compares: per field (name, number, type, label, type_name, proto3_optional, oneof_index)."""
     import os
     import re
-    from google.protobuf import descriptor_pb2
-    if not os.path.exists(REF_PB2):
-        pytest.skip("reference tree not present")
-    src = open(REF_PB2).read()
-    m = re.search(r"AddSerializedFile\((b'(?:[^'\\]|\\.)*')\)", src)
-    assert m, "serialized descriptor literal not found"
-    return descriptor_pb2.FileDescriptorProto.FromString(ast.literal_eval(m.group(1)))
+    from google.protobuf.descriptor_pb2 import FieldDescriptorProto as F
+    src = open(os.path.join(os.path.dirname(proto.__file__), "node_service.proto")).read()
+    src = re.sub(r"//[^\n]*", "", src)
+    scalar = {"string": F.TYPE_STRING, "bool": F.TYPE_BOOL, "bytes": F.TYPE_BYTES, "int32": F.TYPE_INT32}
+    package = re.search(r"package\s+([\w.]+)\s*;", src).group(1)
+    syntax = re.search(r'syntax\s*=\s*"(\w+)"\s*;', src).group(1)
+    msgs = {}
+    for name, body in re.findall(r"message\s+(\w+)\s*\{([^}]*)\}", src):
+        fields = []
+        for mod, typ, fname, num in re.findall(r"(optional|repeated)?\s*([\w.]+)\s+(\w+)\s*=\s*(\d+)\s*;", body):
+            fields.append((fname, int(num), scalar.get(typ, F.TYPE_MESSAGE),
+                           F.LABEL_REPEATED if mod == "repeated" else F.LABEL_OPTIONAL,
+                           "" if typ in scalar else f".{package}.{typ}", mod == "optional",
+                           0 if mod == "optional" else None))
+        msgs[name] = fields
+    svcs = {}
+    for name, body in re.findall(r"service\s+(\w+)\s*\{([^}]*)\}", src):
+        svcs[name] = [(m, f".{package}.{i}", f".{package}.{o}", False, False) for m, i, o in
+                      re.findall(r"rpc\s+(\w+)\s*\(\s*(\w+)\s*\)\s*returns\s*\(\s*(\w+)\s*\)\s*;", body)]
+    return package, syntax, msgs, svcs
 
 
-def test_descriptor_matches_reference_field_by_field():
+def test_descriptor_matches_proto_file_field_by_field():
+    """The descriptor that ``wire/proto.py`` assembles by hand is the one the
+    committed ``node_service.proto`` declares: every message, field number,
+    type, label, proto3 ``optional`` and every service method."""
     from google.protobuf import descriptor_pb2
-    ref = _reference_descriptor()
+    package, syntax, want_msgs, want_svcs = _proto_file_tables()
     ours = descriptor_pb2.FileDescriptorProto()
     proto.FILE_DESCRIPTOR.CopyToProto(ours)
-    assert ours.package == ref.package == "node_service"
-    assert ours.syntax == ref.syntax
+    assert ours.package == package == "node_service"
+    assert ours.syntax == syntax
+    assert len(want_msgs) == 7 and sum(len(f) for f in want_msgs.values()) == 11  # the parser saw the whole file
 
     def msgs(fd):
         return {m.name: [(f.name, f.number, f.type, f.label, f.type_name, f.proto3_optional, f.oneof_index
                           if f.HasField("oneof_index") else None) for f in m.field] for m in fd.message_type}
-    assert msgs(ours) == msgs(ref)
+    assert msgs(ours) == want_msgs
 
     def svcs(fd):
         return {s.name: [(x.name, x.input_type, x.output_type, x.client_streaming, x.server_streaming)
                          for x in s.method] for s in fd.service}
-    assert svcs(ours) == svcs(ref)
+    assert svcs(ours) == want_svcs and len(want_svcs["NodeService"]) == 3

@@ -7,7 +7,7 @@
 # STEP is one of
 #   tests            pytest -m gpu (whole suite, thread timeouts)
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (the driver's default line)
+#   bench            python bench.py --full (the headline and every extra key)
 #   kernels:CFG      rocprofv3 --kernel-trace --stats of bench/gpt_bench.py CFG
 #                    (gpt2 | gpt2xl | llama), summarised by tools/rocprof_summary.py
 #   gaps:CFG         the same trace's inter-kernel gaps (tools/rocprof_gaps.py)
@@ -46,7 +46,7 @@ for step in "$@"; do
         || { echo SMOKE_FAILED; tail -20 ${O}_smoke.log; exit 1; }
       tail -1 ${O}_smoke.log | cut -c1-300 ;;
     bench)
-      timeout -k 10 600 python bench.py > ${O}_bench.json 2> ${O}_bench.err \
+      timeout -k 10 600 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err \
         || { echo BENCH_FAILED; tail -20 ${O}_bench.err; exit 1; }
       cut -c1-600 ${O}_bench.json ;;
     kernels:*|gaps:*)

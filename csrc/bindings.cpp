@@ -144,6 +144,8 @@ PYBIND11_MODULE(_dnn_hip, m) {
   }, py::arg("x"), py::arg("out"), py::arg("w1h"), py::arg("w1l"), py::arg("b1"), py::arg("w2h"), py::arg("w2l"),
         py::arg("b2"), py::arg("B"), py::arg("grid"), py::arg("st"), py::arg("split_out") = 0);
   m.def("cifar_s0_set_wide_store", [](int on) { return dnn_cifar_s0_set_wide_store(on); });
+  m.def("cifar_s0_set_mfma", [](int v) { return dnn_cifar_s0_set_mfma(v); });
+  m.def("cifar_s0_get_mfma", []() { return dnn_cifar_s0_get_mfma(); });
   m.def("cifar_split3", [](u64 a, int lda, u64 o, int ldo, int M, int K, u64 st, int blocked) {
     return dnn_cifar_split3(CFP(a), lda, P(o), ldo, M, K, ST(st), blocked);
   }, py::arg("a"), py::arg("lda"), py::arg("o"), py::arg("ldo"), py::arg("M"), py::arg("K"), py::arg("st"),

@@ -22,7 +22,11 @@
 //    pooled conv1 map double-buffered as hi/lo planes [18][18][32] with the
 //    16-B chunk XORed by (Y & 3), which makes every conv2 ds_read_b128 fragment
 //    (four 16-lane groups) conflict-free; conv2 results leave straight from
-//    the accumulators as 8-B fp32 stores (no LDS staging).
+//    the accumulators as 8-B fp32 stores (no LDS staging).  By default conv2
+//    runs instead on v_mfma_f32_16x16x32_bf16 (template parameter C2 = 1, "conv2
+//    on v_mfma_f32_16x16x32_bf16" below: 1728 of them per image at the same
+//    MFMA cycles, chunk XOR (2*Y & 3), 16-B stores); the 32x32x16 consumer
+//    stays compiled as the A/B's other arm (dnn_cifar_s0_set_mfma).
 //  * cifar_fc1_x3_kernel: fc1 + bias + ReLU on the fp32 boundary tensor, the
 //    split done in registers while staging A (no split copy in HBM): 256x256x32
 //    tiles, 8 waves of 128x64, per k32 step 3 x 32 mfma_f32_16x16x32_bf16 per
@@ -105,13 +109,102 @@ __device__ __forceinline__ void resident_fence(const bf16x8 (&w)[N]) {
   for (int i = 0; i < N; ++i) asm volatile("" ::"v"(w[i]));
 }
 
+// ---------------------------------------------------------------------------
+// conv2 on v_mfma_f32_16x16x32_bf16 (C2 = 1): the same wave work, LDS reads
+// and MFMA cycles as the 32x32x16 path above, on the shape that holds a higher
+// clock under load.  An M tile is a 4x4 pixel block in window-major order
+// (A row m = 8*y1 + 4*x1 + 2*y0 + x0 is pixel (2*y1 + y0, 2*x1 + x0)), so the
+// four accumulator rows of a lane (4*(lane>>4)..+3) are one 2x2 pool window;
+// an N tile is 16 output channels; one K = 32 step is one tap over the 32
+// input channels.  The 16-B chunk of plane row Y is XORed by (2*Y & 3): every
+// ds_read_b128 lane group of a tile then hits 16 distinct slots for all 9 taps
+// (Y & 3, conflict-free for 32x8 tiles, is 2-way conflicted for 4x4 blocks).
+// ---------------------------------------------------------------------------
+template <int C2>
+__device__ __forceinline__ int a1_swz(int Y) {
+  return C2 ? (2 * Y) & 3 : Y & 3;
+}
+
+// A-fragment immediate offset of half-step T (tap = T>>1, M tiles 2*(T&1) + J), plane LO
+template <int T, int J, int LO>
+__device__ __forceinline__ constexpr int m16_imm() {
+  return (((T >> 1) / 3) * 18 + 4 * (2 * (T & 1) + J) + (T >> 1) % 3) * 64 + LO * A1PL;
+}
+
+// 4 reads of half-step T: [hi m0, hi m1, lo m0, lo m1]; the base depends on the parity of ky only
+template <int T>
+__device__ __forceinline__ void m16_issue(const uint32_t (&b)[2], bf16x8 (&a)[4]) {
+  constexpr int kyp = ((T >> 1) / 3) & 1;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(a[0]) : "v"(b[kyp]), "i"(m16_imm<T, 0, 0>()));
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(a[1]) : "v"(b[kyp]), "i"(m16_imm<T, 1, 0>()));
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(a[2]) : "v"(b[kyp]), "i"(m16_imm<T, 0, 1>()));
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(a[3]) : "v"(b[kyp]), "i"(m16_imm<T, 1, 1>()));
+}
+
+// half-step T: issue T+1's reads, wait for T's (counted lgkmcnt, no other LDS
+// op in flight), then 12 MFMAs over 4 accumulators (2 M x 2 N), term-major so
+// that consecutive MFMAs never share an accumulator.
+template <int T>
+__device__ __forceinline__ void m16_step(const uint32_t (&b)[2], const bf16x8 (&wh)[2][9], const bf16x8 (&wl)[2][9],
+                                         f32x4 (&acc)[4][2], bf16x8 (&cur)[4], bf16x8 (&nxt)[4]) {
+  constexpr int tap = T >> 1, m0 = 2 * (T & 1);
+  if constexpr (T + 1 < 18) {
+    m16_issue<T + 1>(b, nxt);
+    asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
+  } else {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int term = 0; term < 3; ++term)
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc[m0 + j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur[(term == 2 ? 2 : 0) + j],
+                                                                  term == 1 ? wl[nt][tap] : wh[nt][tap], acc[m0 + j][nt], 0, 0, 0);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (T + 1 < 18) m16_step<T + 1>(b, wh, wl, acc, nxt, cur);
+}
+
+// bias + ReLU + in-lane 2x2 max-pool of N tile NT of a band (PY = its pooled
+// row for this lane): lane row q = lane>>4 holds pooled column 2*mt + (q & 1)
+// of M tile mt, so lanes l and l^16 hold the columns of opposite parity of the
+// same (oc, PY); one v_permlane16_swap per dword hands the even row columns
+// 0-3 and the odd row columns 4-7: one 16-B store per lane (8-B hi + 8-B lo in
+// the blocked encoding, the split of the same fp32 values).
+template <bool SPLIT_OUT, int NT>
+__device__ __forceinline__ void m16_epilogue(const f32x4 (&acc)[4][2], float bias, float* img, int oc, int PY, int x1) {
+  float v[4];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const f32x4& a = acc[mt][NT];
+    v[mt] = fmaxf(fmax_nan(fmax_nan(a[0], a[1]), fmax_nan(a[2], a[3])) + bias, 0.f);
+  }
+  const auto s0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[0]), __float_as_uint(v[2]), false, false);
+  const auto s1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[1]), __float_as_uint(v[3]), false, false);
+  if constexpr (SPLIT_OUT) {  // k = oc*64 + PY*8 + 4*x1 + 0..3
+    uint2 hi, lo;
+    split2(__uint_as_float(s0[0]), __uint_as_float(s0[1]), hi.x, lo.x);
+    split2(__uint_as_float(s1[0]), __uint_as_float(s1[1]), hi.y, lo.y);
+    char* bp = reinterpret_cast<char*>(img) + (oc * 2 + (PY >> 2)) * 128 + ((PY & 3) * 8 + 4 * x1) * 2;
+    *reinterpret_cast<uint2*>(bp) = hi;
+    *reinterpret_cast<uint2*>(bp + 64) = lo;
+  } else {
+    *reinterpret_cast<uint4*>(img + oc * 64 + PY * 8 + 4 * x1) = make_uint4(s0[0], s0[1], s1[0], s1[1]);
+  }
+}
+
 }  // namespace x3
 
 using namespace x3;
 
 // SPLIT_OUT: the boundary leaves in the blocked hi/lo encoding
 // (cifar_split_blocked_kernel) that cifar_fc1_x3_kernel<true> stages by DMA.
-template <bool WIDE, bool SPLIT_OUT>
+// C2: conv2 consumer path.  0: v_mfma_f32_32x32x16_bf16 (32x8-pixel M tiles);
+// 1: v_mfma_f32_16x16x32_bf16 (4x4-pixel M tiles, 16-B stores only), the default:
+// the same MFMA cycles, a higher clock held under load (docs/ARCHITECTURE.md §2).
+template <bool WIDE, bool SPLIT_OUT, int C2 = 0>
 __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
     const float* __restrict__ x, float* __restrict__ out, const bf16_t* __restrict__ w1h,
     const bf16_t* __restrict__ w1l, const float* __restrict__ b1, const bf16_t* __restrict__ w2h,
@@ -205,7 +298,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       wl.x = hi2 ? rcl : ml;
       wl.y = hi2 ? ml : rcl;
       const int Y = 2 * ty + (q >> 1) + 1, X = 4 * tx + 2 * h + (q & 1) + 1;
-      const int o = (Y * 18 + X) * 64 + ((((cb >> 3) ^ (Y & 3))) << 4) + (cb & 7) * 2;
+      const int o = (Y * 18 + X) * 64 + ((((cb >> 3) ^ a1_swz<C2>(Y))) << 4) + (cb & 7) * 2;
       *reinterpret_cast<uint2*>(smem + a1_off(k, 0) + o) = wh;
       *reinterpret_cast<uint2*>(smem + a1_off(k, 1) + o) = wl;
     };
@@ -256,6 +349,54 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
           if (it + 2 < n) load_img(it + 2);
         }
       }
+      __syncthreads();
+    }
+  } else if constexpr (C2 != 0) {
+    const int m = lane & 15, q16 = lane >> 4, y1 = q16 >> 1, x1 = q16 & 1;
+    const int oc = (rw & 1) * 32 + m;  // N tile nt: oc + 16*nt
+    bf16x8 w2hf[2][9], w2lf[2][9];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        w2hf[nt][tap] = *reinterpret_cast<const bf16x8*>(w2h + (oc + 16 * nt) * 288 + tap * 32 + q16 * 8);
+        w2lf[nt][tap] = *reinterpret_cast<const bf16x8*>(w2l + (oc + 16 * nt) * 288 + tap * 32 + q16 * 8);
+      }
+    const float bias0 = b2[oc], bias1 = b2[oc + 16];
+    resident_fence(w2hf[0]);
+    resident_fence(w2hf[1]);
+    resident_fence(w2lf[0]);
+    resident_fence(w2lf[1]);
+    asm volatile("" ::"v"(bias0), "v"(bias1));
+    // lane base per parity of ky: pixel (py, px) of the 4x4 block, chunk q16 ^ swizzle of row
+    // Y = 4*ty2 + py + ky (4*ty2 even: the XOR depends on the parity of py + ky only)
+    const int py = 2 * (m >> 3) + ((m >> 1) & 1), px = 2 * ((m >> 2) & 1) + (m & 1);
+    uint32_t lb[2];
+#pragma unroll
+    for (int kyp = 0; kyp < 2; ++kyp) lb[kyp] = (uint32_t)((py * 18 + px) * 64 + ((q16 ^ a1_swz<C2>(py + kyp)) << 4));
+
+    auto conv2_img = [&](int k) {  // conv2 + bias + ReLU + pool of image k -> out
+      float* img = out + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 4096;
+      const uint32_t plane = (uint32_t)(uintptr_t)(smem + a1_off(k, 0));
+#pragma unroll 1
+      for (int p = 0; p < 2; ++p) {
+        const int ty2 = (rw >> 1) * 2 + p;
+        const uint32_t rb = plane + ty2 * 4 * 18 * 64;
+        const uint32_t b[2] = {rb + lb[0], rb + lb[1]};
+        f32x4 acc[4][2];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) acc[mt][0] = acc[mt][1] = f32x4{};
+        bf16x8 a0[4], a1[4];
+        m16_issue<0>(b, a0);
+        m16_step<0>(b, w2hf, w2lf, acc, a0, a1);
+        m16_epilogue<SPLIT_OUT, 0>(acc, bias0, img, oc, 2 * ty2 + y1, x1);
+        m16_epilogue<SPLIT_OUT, 1>(acc, bias1, img, oc + 16, 2 * ty2 + y1, x1);
+      }
+    };
+
+    __syncthreads();
+    for (int it = 0; it <= n; ++it) {
+      if (it >= 1) conv2_img(it - 1);
       __syncthreads();
     }
   } else {
@@ -695,8 +836,19 @@ __global__ __launch_bounds__(256) void cifar_head_tail_x3_kernel(const float* __
 
 using namespace dnn;
 
-// stage-0 boundary stores: 16-B (permlane32-paired, 1) or 8-B (0); A/B switch
+// stage-0 boundary stores of the 32x32x16 conv2 path: 16-B (permlane32-paired, 1) or 8-B (0); A/B switch
 static int g_s0_wide_store = 1;
+// conv2 MFMA shape: 1 = 16x16x32 (default; every interleaved round faster than 32x32x16,
+// profiles/cifar_s0_mfma16_ab.jsonl), 0 = 32x32x16 (the A/B's other arm)
+static int g_s0_mfma = 1;
+
+extern "C" int dnn_cifar_s0_set_mfma(int v) {
+  if (v < 0 || v > 1) return 1;
+  g_s0_mfma = v;
+  return 0;
+}
+
+extern "C" int dnn_cifar_s0_get_mfma() { return g_s0_mfma; }
 
 extern "C" int dnn_cifar_s0_set_wide_store(int on) {
   g_s0_wide_store = on ? 1 : 0;
@@ -706,7 +858,10 @@ extern "C" int dnn_cifar_s0_set_wide_store(int on) {
 template <bool SPLIT_OUT>
 static int launch_stage0_x3(const float* x, float* out, const void* w1h, const void* w1l, const float* b1,
                             const void* w2h, const void* w2l, const float* b2, int B, int grid, hipStream_t st) {
-  if (g_s0_wide_store)
+  if (g_s0_mfma == 1)
+    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT, 1>), dim3(grid), dim3(512), 0, st, x, out,
+                       (const bf16_t*)w1h, (const bf16_t*)w1l, b1, (const bf16_t*)w2h, (const bf16_t*)w2l, b2, B);
+  else if (g_s0_wide_store)
     hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT>), dim3(grid), dim3(512), 0, st, x, out,
                        (const bf16_t*)w1h, (const bf16_t*)w1l, b1, (const bf16_t*)w2h, (const bf16_t*)w2l, b2, B);
   else

@@ -158,6 +158,18 @@ def set_stage0_grid(grid: int = 0) -> None:
     STAGE0_GRID = int(grid)
 
 
+STAGE0_MFMA = {"32x32x16": 0, "16x16x32": 1}  # compiled conv2 consumer paths (fp32); 1 is the default
+
+
+def set_stage0_mfma(shape) -> int:
+    """Select the MFMA shape of the fp32 stage-0 conv2 consumer (a key or value
+    of ``STAGE0_MFMA``); returns the previous setting so callers can restore it."""
+    v = STAGE0_MFMA[shape] if isinstance(shape, str) else int(shape)
+    prev = lib().cifar_s0_get_mfma()
+    check(lib().cifar_s0_set_mfma(v), "cifar_s0_set_mfma")
+    return prev
+
+
 def _check_act(t: torch.Tensor, shape, dtype, what: str) -> None:
     if t.dtype != dtype or tuple(t.shape[1:]) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{what}: expected contiguous {dtype} (B,{','.join(map(str, shape))}), "

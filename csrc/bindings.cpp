@@ -216,6 +216,14 @@ PYBIND11_MODULE(_dnn_hip, m) {
     return dnn_sample_topk(CP(x), ld, M, N, reinterpret_cast<int*>(out), temperature, topk, seed,
                            reinterpret_cast<const int*>(step), ST(st));
   });
+  m.def("sample_rows", [](u64 x, int ld, int M, int N, u64 out, float temperature, int topk, float top_p, float min_p,
+                          unsigned seed, u64 step, u64 st, u64 out2, u64 pos_inc, u64 hist, int hist_ld, u64 thr_out) {
+    return dnn_sample_rows(CP(x), ld, M, N, IP(out), temperature, topk, top_p, min_p, seed,
+                           reinterpret_cast<const int*>(step), ST(st), IP(out2), IP(pos_inc), IP(hist), hist_ld,
+                           IP(thr_out));
+  }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("out"), py::arg("temperature"), py::arg("topk"),
+     py::arg("top_p"), py::arg("min_p"), py::arg("seed"), py::arg("step"), py::arg("st"), py::arg("out2") = 0,
+     py::arg("pos_inc") = 0, py::arg("hist") = 0, py::arg("hist_ld") = 0, py::arg("thr_out") = 0);
   m.def("argmax_rows", [](u64 x, int ld, int M, int N, u64 out, int f32in, u64 st, u64 out2, u64 pos_inc, u64 part,
                           u64 hist, int hist_ld) {
     return dnn_argmax_rows(CP(x), ld, M, N, IP(out), f32in, ST(st), IP(out2), IP(pos_inc),

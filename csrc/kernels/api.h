@@ -117,6 +117,11 @@ int dnn_attn_decode(const void* q, const void* kc, const void* vc, void* o, int 
                     const int* lens, float scale, int splits, float* ws, hipStream_t st, int kv8 = 0);
 int dnn_sample_topk(const void* x, int ld, int M, int N, int* out, float temperature, int topk, unsigned seed,
                     const int* step, hipStream_t st);
+// temperature -> top-k -> top-p -> min-p -> draw, with the decode step tail of
+// dnn_argmax_rows (sample_filter.hip); thr_out (optional): each row's final key threshold
+int dnn_sample_rows(const void* x, int ld, int M, int N, int* out, float temperature, int topk, float top_p,
+                    float min_p, unsigned seed, const int* step, hipStream_t st, int* out2 = nullptr,
+                    int* pos_inc = nullptr, int* hist = nullptr, int hist_ld = 0, int* thr_out = nullptr);
 int dnn_argmax_rows(const void* x, int ld, int M, int N, int* out, int f32in, hipStream_t st, int* out2 = nullptr,
                     int* pos_inc = nullptr, void* part = nullptr, int* hist = nullptr, int hist_ld = 0);
 int dnn_quant_fp8_rows(const void* x, int ldx, void* q, float* scale, int M, int K, int kpad, hipStream_t st,

@@ -2,6 +2,7 @@
 // numpy semantics). Replaces the host-side np.argmax of the reference
 // (node.py:61,190), done per row instead of over the flattened batch.
 #include "common.h"
+#include "sampler_common.h"  // argmax_merge, step_tail, bf16_key, mix32, key_to_f
 
 namespace dnn {
 
@@ -9,28 +10,9 @@ namespace dnn {
 // before the first compare (NV per lane, unrolled), so a row costs one memory
 // round trip instead of one per 2048-element sweep (Llama-3's 128K vocabulary
 // at batch 1: one 1024-thread workgroup, 16 loads per lane).  Decode step tail
-// fused in: the token also goes to `out2` (the next step's input ids) and
-// `pos_inc[row]` advances by one, so the sampled id, the input-id copy and the
-// position update are one launch instead of three.
-__device__ __forceinline__ void argmax_merge(float& best, int& bi, float v, int i) {
-  if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-}
-
-// Token history (multi-step decode graphs): `hist[row * hist_ld + pos]` gets
-// the sampled id at the row's position before the advance, so K decode steps
-// replayed as one graph leave every step's token in device memory (no host
-// bookkeeping per step); positions outside [0, hist_ld) are not written.
-__device__ __forceinline__ void step_tail(int row, int bi, int* out, int* out2, int* pos_inc, int* hist,
-                                          int hist_ld) {
-  out[row] = bi;
-  if (out2 != nullptr) out2[row] = bi;
-  if (pos_inc != nullptr) {
-    const int p = pos_inc[row];
-    if (hist != nullptr && p >= 0 && p < hist_ld) hist[(size_t)row * hist_ld + p] = bi;
-    pos_inc[row] = p + 1;
-  }
-}
-
+// fused in (step_tail): the token also goes to `out2` (the next step's input
+// ids) and `pos_inc[row]` advances by one, so the sampled id, the input-id copy
+// and the position update are one launch instead of three.
 template <bool F32, int TH, int NV>
 __global__ __launch_bounds__(TH) void argmax_rows_kernel(const void* __restrict__ xv, int ld, int M, int N,
                                                          int* __restrict__ out, int* __restrict__ out2,
@@ -174,23 +156,6 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const int2* __restric
 // HIP graph serves every decode step (step = the row's position, in device
 // memory) and the result is reproducible.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t bf16_key(short v) {
-  const uint32_t u = (uint16_t)v;
-  return (u & 0x8000u) ? (~u & 0xFFFFu) : (u | 0x8000u);
-}
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
-__device__ __forceinline__ float key_to_f(uint32_t k) {
-  const uint32_t u = (k & 0x8000u) ? (k & 0x7FFFu) : (~k & 0xFFFFu);
-  return __uint_as_float(u << 16);
-}
-
 template <int NV, int TH>
 __global__ __launch_bounds__(TH) void sample_topk_kernel(const bf16_t* __restrict__ x, int ld, int M, int N,
                                                            int* __restrict__ out, float inv_temp, int topk,

@@ -207,10 +207,10 @@ def build_stage(ctx: NodeContext, part: int, ranges, device: torch.device, full_
                                     max_batch=n_seq, max_seq=n_pos, max_tokens=ntok,
                                     temperature=pipe.temperature, top_k=pipe.top_k, seed=pipe.seed,
                                     kv_dtype=pipe.kv_cache_dtype, kv_scale=pipe.kv_cache_scale,
-                                    fp8_prefill=pipe.fp8_prefill)
+                                    fp8_prefill=pipe.fp8_prefill, top_p=pipe.top_p, min_p=pipe.min_p)
     else:
         st = TorchStage(pipe.model, sd, a, b, first, last, device,
-                        sampling=(pipe.temperature, pipe.top_k, pipe.seed))
+                        sampling=(pipe.temperature, pipe.top_k, pipe.seed, pipe.top_p, pipe.min_p))
     log(f"[{ctx.node_id}] Successfully loaded weights into stage {part} (layers [{a},{b}]) on {device}.")
     return st, full_sd
 

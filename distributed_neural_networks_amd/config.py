@@ -12,7 +12,7 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
 * Additive optional fields (absent in the reference file, so it still loads):
   top level ``model``, ``dtype``, ``transport``, ``micro_batch_size``,
   ``num_microbatches``, ``seq_len``, ``decode_steps``, ``prompt_len``, ``temperature``, ``top_k``,
-  ``seed``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
+  ``top_p``, ``min_p``, ``seed``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
   ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``; per node
   ``layers: [start, end]`` (inclusive, as in
   ``partitions/gpt_model_parts.py:12``) and ``device``.
@@ -74,6 +74,8 @@ class PipelineConfig:
     prefill_chunk: int = 0                    # > 0: chunked prefill, this many prompt tokens per stage call
     temperature: float = 0.0                  # 0 = greedy; > 0 = sampling (last stage)
     top_k: int = 0                            # 0 = whole vocabulary
+    top_p: float = 1.0                        # nucleus: smallest head of the distribution with this mass (1 = off)
+    min_p: float = 0.0                        # drop tokens below this fraction of the top probability (0 = off)
     seed: int = 0                             # sampling seed (counter-based RNG, reproducible)
     rpc_timeout_s: Optional[float] = None     # per-hop SendTensor deadline (reference: none)
     health_timeout_s: float = 120.0           # readiness barrier before stage 0 sends
@@ -212,6 +214,12 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
     t = cfg.get("temperature", 0.0)
     if not isinstance(t, (int, float)) or t < 0:
         raise ConfigError(f"ERROR: 'temperature' must be >= 0, got {t!r}")
+    tp = cfg.get("top_p", 1.0)
+    if not isinstance(tp, (int, float)) or isinstance(tp, bool) or not 0 < tp <= 1:
+        raise ConfigError(f"ERROR: 'top_p' must be in (0, 1], got {tp!r}")
+    mp = cfg.get("min_p", 0.0)
+    if not isinstance(mp, (int, float)) or isinstance(mp, bool) or not 0 <= mp < 1:
+        raise ConfigError(f"ERROR: 'min_p' must be in [0, 1), got {mp!r}")
     ret = cfg.get("return_to_node_id")
     if ret is not None and transport in DIST_TRANSPORTS:
         rn = next((n for n in nodes if n.id == ret), None)
@@ -226,6 +234,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         prompt_len=cfg.get("prompt_len"), decode_steps=int(cfg.get("decode_steps", 0)),
         prefill_chunk=int(cfg.get("prefill_chunk", 0)),
         temperature=float(cfg.get("temperature", 0.0)), top_k=int(cfg.get("top_k", 0)), seed=int(cfg.get("seed", 0)),
+        top_p=float(tp), min_p=float(mp),
         rpc_timeout_s=cfg.get("rpc_timeout_s"), health_timeout_s=float(cfg.get("health_timeout_s", 120.0)),
         comm_timeout_s=float(cfg.get("comm_timeout_s", 300.0)),
         heartbeat_timeout_s=float(cfg.get("heartbeat_timeout_s", 15.0)),

@@ -39,6 +39,8 @@ PER_FILE_FLAGS = {"cifar_fused.hip": ["-ffast-math"],
                   # flash / decode softmax maxima over MFMA results: no v_max canonicalise
                   # per score (52 -> 17 v_max per GPT-2 flash block); -inf masking is kept
                   "attention.hip": ["-fno-honor-nans"] + NO_SLP,
+                  # scalar fp32 reductions (probability masses) next to 32-bit VALU reads
+                  "sample_filter.hip": NO_SLP,
                   "gemm_skinny.hip": NO_SLP,
                   "gemm_bf16.hip": NO_SLP}
 

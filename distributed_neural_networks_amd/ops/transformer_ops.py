@@ -286,3 +286,40 @@ def sample_topk(logits: torch.Tensor, out: torch.Tensor, n: int, temperature: fl
     check(lib().sample_topk(ptr(logits), logits.stride(0), M, n, ptr(out), float(temperature), int(top_k),
                             int(seed) & 0xFFFFFFFF, ptr(step), stream_ptr()), "sample_topk")
     return out
+
+
+SAMPLE_FUSED_TAIL = True  # sampling last stage fuses the decode step tail (A/B switch, bench/probes/sample_decode_ab.py)
+
+
+def sample_rows(logits: torch.Tensor, out: torch.Tensor, n: int, temperature: float, top_k: int = 0,
+                top_p: float = 1.0, min_p: float = 0.0, seed: int = 0, step: Optional[torch.Tensor] = None,
+                also: Optional[torch.Tensor] = None, advance: Optional[torch.Tensor] = None,
+                hist: Optional[torch.Tensor] = None, thr_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Temperature -> top-k -> top-p (nucleus) -> min-p sampling per row of bf16
+    logits (sample_filter.hip; ``runtime/sampling.sample_ref`` is the mirror),
+    with the decode step tail of ``argmax_rows`` in the same launch: ``also``
+    receives a copy of the ids, ``hist[row, advance[row]]`` the id and
+    ``advance[row] += 1``.  ``step`` (device int32 per row) seeds the draw per
+    decode step; it defaults to ``advance`` (the position before the
+    increment).  ``thr_out`` (int32, tests): each row's final key threshold."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("sample_rows: bf16 (M, >= n) logits with contiguous rows expected")
+    if not temperature > 0:
+        raise ValueError("sample_rows: temperature must be > 0 (use argmax_rows for greedy)")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"sample_rows: top_p must be in (0, 1], got {top_p!r}")
+    if not 0.0 <= min_p < 1.0:
+        raise ValueError(f"sample_rows: min_p must be in [0, 1), got {min_p!r}")
+    M = logits.shape[0]
+    if not 0 < n <= logits.shape[1]:
+        raise ValueError(f"sample_rows: n = {n} outside the row width {logits.shape[1]}")
+    for t, nm in ((out, "out"), (also, "also"), (advance, "advance"), (step, "step"), (thr_out, "thr_out")):
+        if t is not None and (t.dtype != torch.int32 or t.numel() < M or not t.is_contiguous()):
+            raise ValueError(f"sample_rows: {nm} must be contiguous int32 with >= {M} entries")
+    hist_ld = check_hist(hist, advance, M, "sample_rows")
+    if step is None:
+        step = advance
+    check(lib().sample_rows(ptr(logits), logits.stride(0), M, n, ptr(out), float(temperature), int(top_k),
+                            float(top_p), float(min_p), int(seed) & 0xFFFFFFFF, ptr(step), stream_ptr(), ptr(also),
+                            ptr(advance), ptr(hist), hist_ld, ptr(thr_out)), "sample_rows")
+    return out

@@ -6,6 +6,10 @@ its bit-compatible torch mirror for the CPU/gloo golden path and the tests:
     token = argmax_{i : key(x_i) >= key(k-th largest)} ( x_i / T + G_i ),
     G_i = -log(-log(U_i)),  U_i = hash(seed, row, step[row], i)
 
+``sample_rows`` (csrc/kernels/sample_filter.hip) adds the nucleus (top-p) and
+min-p filters, each one more threshold on the same 16-bit key
+(``filter_thresholds``); ``sample_ref`` mirrors it.
+
 The counter-based hash needs no RNG state (one captured HIP graph serves every
 decode step; runs are reproducible from ``seed``).  The reference has no
 sampler at all: ``np.argmax`` on the host (``node.py:61,190``).
@@ -43,6 +47,13 @@ def sample_topk_ref(logits: torch.Tensor, temperature: float, top_k: int = 0, se
         thr = keys.sort(dim=1, descending=True).values[:, top_k - 1:top_k]
     else:
         thr = torch.zeros((M, 1), dtype=torch.int64)
+    return _draw(x, keys, thr, temperature, seed, step)
+
+
+def _draw(x: torch.Tensor, keys: torch.Tensor, thr: torch.Tensor, temperature: float, seed: int,
+          step: Optional[torch.Tensor]) -> torch.Tensor:
+    """Gumbel-max over ``keys >= thr`` (x bf16 (M, N) on the CPU, thr (M, 1))."""
+    M, N = x.shape
     st = (step.cpu().to(torch.int64) if step is not None else torch.zeros(M, dtype=torch.int64)) & _M32
     rows = torch.arange(M, dtype=torch.int64)
     inner = _mix32(st + 0x632BE5AB)
@@ -56,9 +67,81 @@ def sample_topk_ref(logits: torch.Tensor, temperature: float, top_k: int = 0, se
     return score.argmax(dim=1).to(torch.int32)
 
 
+def _key_values() -> torch.Tensor:
+    """The fp32 value of every 16-bit key (the kernel's ``key_to_f``)."""
+    k = torch.arange(65536, dtype=torch.int64)
+    u = torch.where((k & 0x8000) != 0, k & 0x7FFF, (~k) & 0xFFFF)
+    bits = u << 16
+    return torch.where(bits >= 1 << 31, bits - (1 << 32), bits).to(torch.int32).view(torch.float32)
+
+
+def filter_thresholds(logits: torch.Tensor, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                      min_p: float = 0.0) -> torch.Tensor:
+    """Per-row key threshold (M, 1) of the device sampler's filter chain
+    (``sample_rows``, csrc/kernels/sample_filter.hip): the kept set is
+    ``key_i >= max(thr_k, thr_p, thr_m)`` with
+
+    * ``thr_k`` the k-th largest key (0 when top_k is off);
+    * ``thr_p`` the largest key t with ``sum_{key_i >= t} w_i >= top_p * Z``,
+      ``w_i = exp((x_i - x_max) / T)`` over the top-k survivors, ``Z = sum w_i``
+      (masses in float64; ``top_p >= 1`` switches it off);
+    * ``thr_m`` the smallest key whose value passes ``(x - x_max) / T >=
+      log(min_p)`` in fp32, never above the row maximum (``min_p <= 0``: off)."""
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+    if not 0.0 <= min_p < 1.0:
+        raise ValueError(f"min_p must be in [0, 1), got {min_p!r}")
+    x = logits.to(torch.bfloat16).cpu()
+    M, N = x.shape
+    keys = _keys(x)
+    skeys = keys.sort(dim=1, descending=True).values
+    thr = skeys[:, top_k - 1:top_k].clone() if 0 < top_k < N else torch.zeros((M, 1), dtype=torch.int64)
+    if not (top_p < 1.0 or min_p > 0.0):
+        return thr
+    inv_t = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(temperature, dtype=torch.float32)
+    kval = _key_values()
+    kmax = skeys[:, :1]
+    xmax = kval[kmax]  # (M, 1) fp32
+    if top_p < 1.0:
+        w = torch.exp(((kval[skeys] - xmax) * inv_t).double())
+        w = torch.where(skeys >= thr, w, torch.zeros_like(w))  # thr is thr_k here
+        need = float(torch.tensor(top_p, dtype=torch.float32)) * w.sum(dim=1, keepdim=True)
+        # descending keys: the first position whose running mass reaches `need`
+        # holds the boundary key (the mass of `key >= t` includes all of t's ties)
+        j = (w.cumsum(dim=1) >= need).to(torch.int8).argmax(dim=1, keepdim=True)
+        thr = torch.maximum(thr, skeys.gather(1, j))
+    if min_p > 0.0:
+        lmp = torch.log(torch.tensor(min_p, dtype=torch.float32).double()).float()
+        ok = ((kval[None, :0xFF81] - xmax) * inv_t) >= lmp  # (M, keys up to +inf), monotone in the key
+        first = torch.where(ok.any(dim=1, keepdim=True), ok.to(torch.int8).argmax(dim=1, keepdim=True),
+                            torch.full((M, 1), 0xFF81, dtype=torch.int64))
+        thr = torch.maximum(thr, torch.minimum(first, kmax))
+    return thr
+
+
+def sample_ref(logits: torch.Tensor, temperature: float, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
+               seed: int = 0, step: Optional[torch.Tensor] = None, thr: Optional[torch.Tensor] = None,
+               return_thr: bool = False):
+    """Torch mirror of ``sample_rows``: the filter chain of
+    ``filter_thresholds``, then ``sample_topk_ref``'s draw over the kept set.
+    ``thr`` (M,) or (M, 1) overrides the final per-row key threshold (compare
+    only the draw against a device run); ``return_thr`` also returns it (M,)."""
+    x = logits.to(torch.bfloat16).cpu()
+    M, N = x.shape
+    keys = _keys(x)
+    if thr is None:
+        thr = filter_thresholds(x, temperature, top_k, top_p, min_p)
+    thr = thr.cpu().to(torch.int64).reshape(M, 1)
+    ids = _draw(x, keys, thr, temperature, seed, step)
+    return (ids, thr.reshape(M).to(torch.int32)) if return_thr else ids
+
+
 def pick(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0,
-         step: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Greedy when temperature <= 0, else the Gumbel top-k sample (CPU path)."""
+         step: Optional[torch.Tensor] = None, top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
+    """Greedy when temperature <= 0, else the Gumbel sample over the top-k /
+    top-p / min-p survivors (CPU path)."""
     if temperature <= 0:
         return logits.argmax(dim=-1).to(torch.int32)
-    return sample_topk_ref(logits, temperature, top_k, seed, step)
+    if top_p >= 1.0 and min_p <= 0.0:
+        return sample_topk_ref(logits, temperature, top_k, seed, step)
+    return sample_ref(logits, temperature, top_k, top_p, min_p, seed, step)

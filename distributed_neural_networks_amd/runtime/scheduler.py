@@ -320,9 +320,11 @@ class DecodeRing:
         ``decode_rounds`` replays it while K or more rounds remain (single-step
         graphs for the rest): the graph-to-graph boundary after every step's
         argmax (profiles/r4_gpt2_b64_decode_gaps.md) is paid once per K steps.
-        Positions and input ids live on the device; a greedy last stage writes
+        Positions and input ids live on the device; the last stage writes
         each step's token into a device history (``hist``, indexed by
-        position) in its argmax launch, so recording costs nothing per step.
+        position) in its argmax or sampler launch, so recording costs nothing
+        per step (sampled decoding replays the same K-step graphs: the draw is
+        seeded by the position the kernel itself advances).
         -1 = ``$DNN_DECODE_MULTISTEP`` or 8; 0 / 1 = off."""
         self.stages = list(stages)
         self.links = links
@@ -369,7 +371,7 @@ class DecodeRing:
         self.multi_step = int(os.environ.get("DNN_DECODE_MULTISTEP", "8")) if multi_step < 0 else multi_step
         self.graph_k = None  # the K-round graph (capture)
         self.graph_k_steps = 0
-        # device token history (one group, greedy fused tail): hist[m][b, p] =
+        # device token history (one group, fused step tail, greedy or sampled): hist[m][b, p] =
         # the token sampled at position p; tokens() reads it past the prefill
         tail = self.last and getattr(self.stages[-1], "fuses_step_tail", False)
         cap = min((getattr(s, "max_seq", 0) for s in self.stages), default=0)
@@ -391,8 +393,9 @@ class DecodeRing:
 
     def _decode_body(self, m: int):
         x = self.cur[m] if self.first else self.xin[m]
-        # greedy last stage: the argmax launch also writes the next input ids
-        # (one group) and advances the positions — no separate copy / add kernels
+        # last stage with a fused tail: the argmax (greedy) or sampler launch also
+        # writes the next input ids (one group) and advances the positions — no
+        # separate copy / add kernels
         if self.last and getattr(self.stages[-1], "fuses_step_tail", False):
             ids = self.cur[m].view(self.B) if self.G == 1 else None
             adv = (ids, self.pos[m]) if self.hist is None else (ids, self.pos[m], self.hist[m])

@@ -145,7 +145,11 @@ class TorchStage(StageCompute):
     def __init__(self, model: str, sd: Dict[str, torch.Tensor], start: int, end: int, first: bool, last: bool,
                  device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0)):
         from ..models import build_golden_stage
+        # sampling = (temperature, top_k, seed) or (temperature, top_k, seed, top_p, min_p)
+        if len(sampling) not in (3, 5):
+            raise ValueError(f"sampling: 3 or 5 entries expected, got {len(sampling)}")
         self.temperature, self.top_k, self.seed = float(sampling[0]), int(sampling[1]), int(sampling[2])
+        self.top_p, self.min_p = (float(sampling[3]), float(sampling[4])) if len(sampling) == 5 else (1.0, 0.0)
         self.model, self.start, self.end, self.first, self.last = model, start, end, first, last
         self.device = torch.device(device)
         self.family = model_info(model).family
@@ -215,7 +219,8 @@ class TorchStage(StageCompute):
             from .sampling import pick
             logits = y[:, -1, :] if last_only else y.reshape(B * T, -1)
             step = pos if isinstance(pos, torch.Tensor) else torch.full((B,), p, dtype=torch.int32)
-            pred = pick(y[:, -1, :], self.temperature, self.top_k, self.seed, step).to(torch.int32)
+            pred = pick(y[:, -1, :], self.temperature, self.top_k, self.seed, step, top_p=self.top_p,
+                        min_p=self.min_p).to(torch.int32)
             if out is not None and last_only:
                 out.copy_(pred)
                 pred = out

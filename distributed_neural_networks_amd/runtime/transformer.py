@@ -82,7 +82,8 @@ class TransformerStage(StageCompute):
     def __init__(self, model: str, sd: Dict[str, torch.Tensor], start: int, end: int, first: bool, last: bool,
                  device, max_batch: int = 8, max_seq: int = 1024, max_tokens: Optional[int] = None,
                  fp8: bool = False, temperature: float = 0.0, top_k: int = 0, seed: int = 0,
-                 kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3"):
+                 kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
+                 top_p: float = 1.0, min_p: float = 0.0):
         info = model_info(model)
         # fp8 weights, prefill (W8A8) activations: "e4m3" (default) = one e4m3
         # byte per activation, per-row scale, at the fp8 MFMA rate; "split" =
@@ -98,8 +99,14 @@ class TransformerStage(StageCompute):
             raise ValueError(f"fp8_prefill {fp8_prefill!r}: split or e4m3")
         self.fp8_prefill = fp8_prefill
         # sampling (last stage): temperature 0 = greedy argmax; otherwise
-        # Gumbel-max over the top_k logits (0 = all), seeded per (row, position)
+        # Gumbel-max over the top_k logits (0 = all) that also pass the nucleus
+        # (top_p) and min_p filters, seeded per (row, position)
         self.temperature, self.top_k, self.seed = float(temperature), int(top_k), int(seed)
+        self.top_p, self.min_p = float(top_p), float(min_p)
+        if not 0.0 < self.top_p <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+        if not 0.0 <= self.min_p < 1.0:
+            raise ValueError(f"min_p must be in [0, 1), got {min_p!r}")
         self.model, self.family, self.cfg = model, info.family, info.cfg
         self.start, self.end, self.first, self.last = start, end, first, last
         self.device = dev = torch.device(device)
@@ -400,20 +407,21 @@ class TransformerStage(StageCompute):
     # ------------------------------------------------------------------ forward
     @property
     def fuses_step_tail(self) -> bool:
-        """Greedy last stage: ``step(advance=...)`` folds the decode step's tail
-        (input-id copy, position update) into the argmax launch."""
-        return self.last and not self.temperature > 0
+        """Last stage: ``step(advance=...)`` folds the decode step's tail
+        (input-id copy, position update, token history) into the argmax launch
+        (greedy) or the sampler launch (``T_.SAMPLE_FUSED_TAIL``)."""
+        return self.last and (not self.temperature > 0 or T_.SAMPLE_FUSED_TAIL)
 
     def step(self, x: torch.Tensor, pos: torch.Tensor, B: int, T: int, b0: int = 0, out: Optional[torch.Tensor] = None,
              last_only: bool = True, advance=None):
         """Run this stage for B sequences x T new tokens at cache rows
         [b0, b0+B) and positions ``pos`` (device int32 (B,), tokens already
         cached).  Returns hidden (B*T, d) bf16, or StageOutput for the last stage.
-        ``advance`` = (ids or None, positions[, token history]): greedy last stage only
+        ``advance`` = (ids or None, positions[, token history]): last stage only
         (``fuses_step_tail``): the sampled ids are also written to ``ids`` and
-        ``positions += 1``, in the argmax launch."""
+        ``positions += 1``, in the argmax / sampler launch."""
         if advance is not None and not (self.fuses_step_tail and last_only):
-            raise ValueError("step(advance=...) needs a greedy last stage with last_only")
+            raise ValueError("step(advance=...) needs a last stage that fuses the step tail, with last_only")
         ntok = B * T
         if ntok > self.buf_h.shape[0]:
             raise ValueError(f"stage buffers hold {self.buf_h.shape[0]} tokens, got {ntok}")
@@ -525,10 +533,20 @@ class TransformerStage(StageCompute):
                 linear(lnf, self.w_head, None, out=logits[:, :self.V])
         nxt = self.next_ids[r0:r0 + rows]
         if self.temperature > 0 and last_only:
-            T_.sample_topk(logits, nxt, self.V, self.temperature, self.top_k, self.seed, step=pos)
-            if out is not None:
-                out.copy_(nxt)
-            return StageOutput(logits[:, :self.V], nxt)
+            if not T_.SAMPLE_FUSED_TAIL:  # the A/B baseline: sampler launch, then the ids copy (and the ring's tail launches)
+                if self.top_p < 1.0 or self.min_p > 0.0:
+                    T_.sample_rows(logits, nxt, self.V, self.temperature, self.top_k, self.top_p, self.min_p,
+                                   self.seed, step=pos)
+                else:
+                    T_.sample_topk(logits, nxt, self.V, self.temperature, self.top_k, self.seed, step=pos)
+                if out is not None:
+                    out.copy_(nxt)
+                return StageOutput(logits[:, :self.V], nxt)
+            dst = out if out is not None else nxt
+            also, adv, hist = _advance3(advance)
+            T_.sample_rows(logits, dst, self.V, self.temperature, self.top_k, self.top_p, self.min_p, self.seed,
+                           step=pos, also=also, advance=adv, hist=hist)
+            return StageOutput(logits[:, :self.V], dst)
         dst = out if (last_only and out is not None) else nxt
         also, adv, hist = _advance3(advance)
         part = self.amx_part[r0 * 2 * T_.ARGMAX_PART_PER_ROW:] if last_only else None
@@ -580,12 +598,14 @@ def _e4m3_amax(t: torch.Tensor) -> float:
 def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: bool, device, dtype=None,
                        max_batch: int = 8, max_seq: int = 1024, max_tokens: Optional[int] = None,
                        temperature: float = 0.0, top_k: int = 0, seed: int = 0, kv_dtype: str = "bf16",
-                       kv_scale: str = "calibrated", fp8_prefill: str = "e4m3"):
+                       kv_scale: str = "calibrated", fp8_prefill: str = "e4m3", top_p: float = 1.0,
+                       min_p: float = 0.0):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
     info = model_info(model)
     max_seq = min(max_seq, getattr(info.cfg, "block_size", getattr(info.cfg, "max_seq", max_seq)))
     return TransformerStage(model, sd, start, end, first, last, device, max_batch, max_seq, max_tokens, fp8,
-                            temperature, top_k, seed, kv_dtype=kv_dtype, kv_scale=kv_scale, fp8_prefill=fp8_prefill)
+                            temperature, top_k, seed, kv_dtype=kv_dtype, kv_scale=kv_scale, fp8_prefill=fp8_prefill,
+                            top_p=top_p, min_p=min_p)
 
 
 # ---------------------------------------------------------------------- smoke / golden check

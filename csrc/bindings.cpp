@@ -155,6 +155,8 @@ PYBIND11_MODULE(_dnn_hip, m) {
     return dnn_cifar_fc1_x3(CFP(a), lda, CP(wh), CP(wl), ldw, CFP(bias), FP(c), ldc, M, N, K, ST(st), a_split);
   }, py::arg("a"), py::arg("lda"), py::arg("wh"), py::arg("wl"), py::arg("ldw"), py::arg("bias"), py::arg("c"),
         py::arg("ldc"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("st"), py::arg("a_split") = 0);
+  m.def("cifar_fc1_set_sched", [](int v) { return dnn_cifar_fc1_set_sched(v); });
+  m.def("cifar_fc1_get_sched", []() { return dnn_cifar_fc1_get_sched(); });
   m.def("cifar_split_blocked", [](u64 a, u64 o, int M, int K, int dir, u64 st) {
     return dnn_cifar_split_blocked(CFP(a), FP(o), M, K, dir, ST(st));
   });

@@ -92,6 +92,8 @@ int dnn_cifar_s0_get_mfma();
 int dnn_cifar_split3(const float* a, int lda, void* o, int ldo, int M, int K, hipStream_t st, int blocked = 0);
 int dnn_cifar_fc1_x3(const float* A, int lda, const void* Wh, const void* Wl, int ldw, const float* bias, float* C,
                      int ldc, int M, int N, int K, hipStream_t st, int a_split = 0);
+int dnn_cifar_fc1_set_sched(int v);
+int dnn_cifar_fc1_get_sched();
 int dnn_cifar_split_blocked(const float* a, float* o, int M, int K, int dir, hipStream_t st);
 int dnn_cifar_head_tail_x3(const float* hid, const void* w2h, const void* w2l, const float* b2, float* probs, int* pred,
                            int B, hipStream_t st);

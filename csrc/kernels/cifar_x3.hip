@@ -31,6 +31,10 @@
 //    split done in registers while staging A (no split copy in HBM): 256x256x32
 //    tiles, 8 waves of 128x64, per k32 step 3 x 32 mfma_f32_16x16x32_bf16 per
 //    wave (A_hi W_hi + A_hi W_lo + A_lo W_hi) on 24 conflict-free ds_read_b128.
+//    By default waves 0-3 and 4-7 run half a k-step apart, so each SIMD pairs a
+//    wave issuing MFMAs with one reading, splitting and restaging ("STAG"
+//    below); the lockstep loop stays compiled as the A/B's other arm
+//    (dnn_cifar_fc1_set_sched).
 //  * cifar_split3_kernel: fp32 (B,K) -> bf16 (B,3K) = [hi | hi | lo], the A
 //    operand of the small-batch fc1 (one skinny bf16 GEMM over K' = 3K against
 //    W' = [W_hi | W_lo | W_hi]) when the 256^2 tiles cannot fill the chip.
@@ -513,8 +517,9 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
 // four ds_read_b128 lane groups ({0-3,12-15,20-27}, ...) of a fragment read
 // (lane: row l & 15, chunk l >> 4) then hit 16 distinct slots, and the A
 // writes (8 contiguous lanes = 2 rows x 4 chunks) 8 distinct ds_write slots.
-// One barrier per k32 step: the step's next-tile loads are issued before its
-// MFMAs and land in the other buffer.
+// Lockstep schedule: one barrier per k32 step, the step's next-tile loads are
+// issued before its MFMAs and land in the other buffer.  Staggered schedule
+// (the default): see STAG at the kernel.
 // ---------------------------------------------------------------------------
 constexpr int F1_T = 256, F1_K = 32, F1_PLANE = 256 * 64;
 
@@ -539,14 +544,41 @@ __device__ __forceinline__ void f1_tile_coords(int logical, int ntm, int ntn, in
 // split+store between the two MFMA halves (flat), a second register set for A
 // two k-steps ahead once the loads were coalesced (flat, 6 spilled VGPRs).  Probes
 // (profiles/archive/r2_cifar_fc1_probes.jsonl): without the A stream the kernel runs
-// 0.51 ms, without any load 0.45 ms (1.8 PF/s), with both 0.80 ms.
+// 0.51 ms, without any load 0.45 ms (1.8 PF/s), with both 0.80 ms.  On the
+// staggered schedule (profiles/cifar_fc1_sched_ab.jsonl): s_setprio 1 around
+// the MFMA segment and static s_setprio 1 for waves 4-7 both lost 0.4-0.5 %;
+// the bias in registers with a branch-free store path for full tiles was a
+// tie on lockstep and -0.75 % with overlapping rounds on staggered: dropped.
 //
 // SPLIT_IN: A arrives pre-split in the blocked boundary encoding (see
 // cifar_split_blocked_kernel: per row and 32-k block, 32 bf16 hi then 32 bf16
 // lo — the same 4 bytes per element as fp32, the same hi/lo this kernel would
 // form in registers), so A is staged by DMA exactly like W: no VGPR round
 // trip, no split ALU, no vmcnt stall on A inside the k loop.
-template <bool SPLIT_IN>
+//
+// STAG: the staggered schedule.  Lockstep (STAG = false), all eight waves read
+// their fragments, multiply and restage at the same time, so a SIMD's matrix
+// pipe idles while both of its waves read or split.  Staggered, group 0 (waves
+// 0-3, rows 0-127 of the tile) and group 1 (waves 4-7) run half a k-step apart:
+// a k-step is two segments between s_barriers, and in each segment one wave of
+// every SIMD issues its 96 MFMAs from 24 fragments already in registers while
+// its partner runs its load segment (split + ds_write of its share of A(t+1),
+// its global loads, the 24 ds_read_b128 of its next MFMA segment).  Segment s:
+//     s = 2t      group 0: load segment of step t     group 1: MFMAs of step t-1
+//     s = 2t + 1  group 0: MFMAs of step t            group 1: load segment of step t
+// Buffer (t+1)&1 is last read (step t-1) in segment 2t-1 and first read (step
+// t+1) in segment 2t+2, so everything that writes it goes into segments 2t and
+// 2t+1: both groups issue its DMAs in segment 2t (group 1 ahead of its MFMAs)
+// and retire them with a counted vmcnt before the barrier that ends segment
+// 2t+1; group 0 writes its A rows in segment 2t, group 1 in segment 2t+1, each
+// behind the lgkmcnt(0) of the segment's barrier.  The A registers are loaded
+// two segments ahead of their split, right after the previous split frees them,
+// and after the step's DMAs in program order, so vmcnt(4) retires the DMAs and
+// leaves the A loads in flight.  Every wave passes 1 + 2 nk barriers for any
+// nk >= 1: group 0 ends with the barrier after its last MFMAs and goes to its
+// epilogue while group 1 runs its last MFMA segment.  Each accumulator sees the
+// same MFMAs in the same order as lockstep: the outputs are bitwise equal.
+template <bool SPLIT_IN, bool STAG = false>
 __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __restrict__ A, int lda,
                                                               const bf16_t* __restrict__ Wh,
                                                               const bf16_t* __restrict__ Wl, int ldw,
@@ -568,18 +600,26 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
   // segments and the split halves land as ds_write_b64 into half of a 16-B LDS
   // chunk.  (The first mapping, 32 contiguous bytes per lane in two loads,
   // touched every 128-B line twice per wave: 0.85 -> 0.68 ms.)
+  // The staging lambdas take their lane addressing from ``ltid`` (= tid).  The
+  // staggered loop hands them a fresh opaque copy per segment (fresh_tid), so
+  // the row pointers and LDS offsets are recomputed under the partner's MFMAs
+  // instead of living in VGPRs across the loop: 128 accumulators + 96 fragment
+  // registers + 16 of A in flight leave 16 for everything else at 2 waves/SIMD.
+  int ltid = tid;
   float4 ar[4];
   auto load_a = [&](int t, auto) {
+    const int x = ltid;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int row = min(m0 + (tid >> 3) + 64 * k, M - 1);
-      ar[k] = *reinterpret_cast<const float4*>(A + (size_t)row * lda + t * F1_K + (tid & 7) * 4);
+      const int row = min(m0 + (x >> 3) + 64 * k, M - 1);
+      ar[k] = *reinterpret_cast<const float4*>(A + (size_t)row * lda + t * F1_K + (x & 7) * 4);
     }
   };
   auto store_a = [&](int u, auto) {
+    const int x = ltid;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int r = (tid >> 3) + 64 * k, c = (tid & 7) >> 1, half = tid & 1;
+      const int r = (x >> 3) + 64 * k, c = (x & 7) >> 1, half = x & 1;
       uint2 hi, lo;
       split2(ar[k].x, ar[k].y, hi.x, lo.x);
       split2(ar[k].z, ar[k].w, hi.y, lo.y);
@@ -592,6 +632,7 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
   // SPLIT_IN: A hi / lo planes by DMA, 2 pieces of 16 rows per wave and plane (as W)
   auto stage_a = [&](int u, int t) {
     const char* Ab = reinterpret_cast<const char*>(A);
+    const int lane = ltid & 63, wave = ltid >> 6;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
 #pragma unroll
@@ -604,6 +645,7 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     }
   };
   auto stage_w = [&](int u, int t) {
+    const int lane = ltid & 63, wave = ltid >> 6;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const bf16_t* W = p ? Wl : Wh;
@@ -632,8 +674,18 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     stage_w(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     store_a(0, I0{});
+    if constexpr (STAG) {
+      if (nk > 1) load_a(1, I0{});  // both groups split A(1) in their first load segment
+    }
   }
-  __syncthreads();
+  if constexpr (STAG) {  // raw barrier: A(1) stays in flight across it
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
+    __syncthreads();
+  }
 
   const int fr = lane & 15, fc = lane >> 4;
   auto compute = [&](int u) {
@@ -674,21 +726,101 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
-  for (int t = 0; t < nk; ++t) {
-    const int u = t & 1;
-    if (t + 1 < nk) {
-      if constexpr (SPLIT_IN)
-        stage_a(u ^ 1, t + 1);
+  if constexpr (!STAG) {
+    for (int t = 0; t < nk; ++t) {
+      const int u = t & 1;
+      if (t + 1 < nk) {
+        if constexpr (SPLIT_IN)
+          stage_a(u ^ 1, t + 1);
+        else
+          load_a(t + 1, I0{});
+        stage_w(u ^ 1, t + 1);
+      }
+      compute(u);
+      if (t + 1 < nk) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (!SPLIT_IN) store_a(u ^ 1, I0{});
+      }
+      barrier();
+    }
+  } else {
+    bf16x8 fbh[4], fbl[4], fah[8], fal[8];
+    auto read_frags = [&](int u) {  // all 24 fragments of a step: 8 W, 16 A
+      const int fr = ltid & 15, fc = (ltid >> 4) & 3, wc = (ltid >> 6) & 3, wr = ltid >> 8;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        fbh[j] = f1_frag(plane(u, 2), wc * 64 + j * 16 + fr, fc);
+        fbl[j] = f1_frag(plane(u, 3), wc * 64 + j * 16 + fr, fc);
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        fah[i] = f1_frag(plane(u, 0), wr * 128 + i * 16 + fr, fc);
+        fal[i] = f1_frag(plane(u, 1), wr * 128 + i * 16 + fr, fc);
+      }
+    };
+    // per accumulator W_hi A_hi, W_lo A_hi, W_hi A_lo as in compute(); term-major
+    // inside a row block so that consecutive MFMAs never share an accumulator
+    auto mfma_seg = [&]() {
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int term = 0; term < 3; ++term)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 1 ? fbl[j] : fbh[j], term == 2 ? fal[i] : fah[i],
+                                                                acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    // retire this wave's DMAs of the next step; the 4 A loads issued after them stay in flight
+    auto retire_dma = [&](bool a_in_flight) {
+      if (a_in_flight)
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       else
-        load_a(t + 1, I0{});
-      stage_w(u ^ 1, t + 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    auto stage_next = [&](int u, int t) {
+      if constexpr (SPLIT_IN) stage_a(u, t);
+      stage_w(u, t);
+    };
+    // One program for both groups, group 1 one barrier behind: it passes an extra
+    // barrier ahead of the loop (segment 0, where it only issues the DMAs of step
+    // 1) and skips the one after its last MFMA segment, which group 0 passes on
+    // its way to the epilogue.  What differs is where a group's DMAs sit: group 0
+    // issues those of step t+1 in its load segment of step t (segment 2t), group 1
+    // ahead of its MFMAs of step t-1 (the same segment 2t).
+    const bool g1 = __builtin_amdgcn_readfirstlane(wr) != 0;
+    auto fresh_tid = [&]() {
+      ltid = tid;
+      asm volatile("" : "+v"(ltid));
+    };
+    if (g1) {
+      if (nk > 1) stage_next(1, 1);
+      barrier();
     }
-    compute(u);
-    if (t + 1 < nk) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if constexpr (!SPLIT_IN) store_a(u ^ 1, I0{});
+    for (int t = 0; t < nk; ++t) {
+      const int u = t & 1;
+      // load segment: group 0 segment 2t, group 1 segment 2t + 1
+      fresh_tid();
+      read_frags(u);
+      if (t + 1 < nk) {
+        if constexpr (!SPLIT_IN) store_a(u ^ 1, I0{});
+        if (!g1) stage_next(u ^ 1, t + 1);
+        if constexpr (!SPLIT_IN) {
+          if (t + 2 < nk) load_a(t + 2, I0{});
+        }
+        if (g1) retire_dma(!SPLIT_IN && t + 2 < nk);
+      }
+      barrier();
+      // MFMA segment: group 0 segment 2t + 1, group 1 segment 2t + 2
+      if (g1 && t + 2 < nk) {
+        fresh_tid();
+        stage_next(u, t + 2);
+      }
+      mfma_seg();
+      if (!g1 && t + 1 < nk) retire_dma(!SPLIT_IN && t + 2 < nk);
+      if (!g1 || t + 1 < nk) barrier();
     }
-    barrier();
   }
 
   // epilogue (transposed accumulators): row m0 + wr*128 + i*16 + (lane & 15), cols n..n+3
@@ -881,18 +1013,36 @@ extern "C" int dnn_cifar_stage0_x3(const float* x, float* out, const void* w1h, 
                    : launch_stage0_x3<false>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st);
 }
 
+// fc1 k-loop schedule: 0 = lockstep, 1 = staggered wave groups (the A/B's two arms, bitwise-equal outputs)
+static int g_fc1_sched = 1;
+
+extern "C" int dnn_cifar_fc1_set_sched(int v) {
+  if (v < 0 || v > 1) return 1;
+  g_fc1_sched = v;
+  return 0;
+}
+
+extern "C" int dnn_cifar_fc1_get_sched() { return g_fc1_sched; }
+
+template <bool SPLIT_IN>
+static int launch_fc1_x3(const float* A, int lda, const void* Wh, const void* Wl, int ldw, const float* bias, float* C,
+                         int ldc, int M, int N, int K, int blocks, hipStream_t st) {
+  if (g_fc1_sched == 1)
+    hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, true>), dim3(blocks), dim3(512), 0, st, A, lda,
+                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
+  else
+    hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, false>), dim3(blocks), dim3(512), 0, st, A, lda,
+                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
+  return (int)hipGetLastError();
+}
+
 extern "C" int dnn_cifar_fc1_x3(const float* A, int lda, const void* Wh, const void* Wl, int ldw, const float* bias,
                                 float* C, int ldc, int M, int N, int K, hipStream_t st, int a_split) {
   if (M <= 0) return 0;
-  if (N % F1_T != 0 || K % F1_K != 0 || lda % 4 != 0 || ldw % 8 != 0 || ldc % 4 != 0) return -1;
+  if (N % F1_T != 0 || K < F1_K || K % F1_K != 0 || lda % 4 != 0 || ldw % 8 != 0 || ldc % 4 != 0) return -1;
   const int blocks = ((M + F1_T - 1) / F1_T) * (N / F1_T);
-  if (a_split)
-    hipLaunchKernelGGL(cifar_fc1_x3_kernel<true>, dim3(blocks), dim3(512), 0, st, A, lda, (const bf16_t*)Wh,
-                       (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
-  else
-    hipLaunchKernelGGL(cifar_fc1_x3_kernel<false>, dim3(blocks), dim3(512), 0, st, A, lda, (const bf16_t*)Wh,
-                       (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
-  return (int)hipGetLastError();
+  return a_split ? launch_fc1_x3<true>(A, lda, Wh, Wl, ldw, bias, C, ldc, M, N, K, blocks, st)
+                 : launch_fc1_x3<false>(A, lda, Wh, Wl, ldw, bias, C, ldc, M, N, K, blocks, st);
 }
 
 extern "C" int dnn_cifar_split_blocked(const float* a, float* o, int M, int K, int dir, hipStream_t st) {

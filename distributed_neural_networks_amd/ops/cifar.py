@@ -170,6 +170,18 @@ def set_stage0_mfma(shape) -> int:
     return prev
 
 
+FC1_SCHED = {"lockstep": 0, "staggered": 1}  # compiled k-loop schedules of the fused fp32 fc1 (cifar_fc1_x3)
+
+
+def set_fc1_sched(sched) -> int:
+    """Select the k-loop schedule of the fused fp32 fc1 (a key or value of
+    ``FC1_SCHED``); returns the previous setting so callers can restore it."""
+    v = FC1_SCHED[sched] if isinstance(sched, str) else int(sched)
+    prev = lib().cifar_fc1_get_sched()
+    check(lib().cifar_fc1_set_sched(v), "cifar_fc1_set_sched")
+    return prev
+
+
 def _check_act(t: torch.Tensor, shape, dtype, what: str) -> None:
     if t.dtype != dtype or tuple(t.shape[1:]) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"{what}: expected contiguous {dtype} (B,{','.join(map(str, shape))}), "

@@ -4,9 +4,11 @@ every round's time and the median, plus the max |difference| of the two
 outputs (0 for wide_store; the MFMA shapes sum K in different orders, so
 ~1e-6 for mfma16).  One JSON line.
 
-    python bench/probes/cifar_s0_ab.py [--switch wide_store|mfma16] [--arms 0,1] [--batch 65536]
+    python bench/probes/cifar_s0_ab.py [--switch wide_store|mfma16|conv1_k32] [--arms 0,1] [--batch 65536]
 
-mfma16 arms: 0 = conv2 on 32x32x16, 1 = on 16x16x32.  An arm wins only if every
+mfma16 arms: 0 = conv2 on 32x32x16, 1 = on 16x16x32.  conv1_k32 arms: 0 = conv1
+on K = 48 (HWC4 input planes), 1 = on K = 32 (channel-packed planes, parity
+weight sets); they sum K in different orders (~1e-6).  An arm wins only if every
 one of its rounds is faster than every round of the other.
 """
 import argparse
@@ -23,8 +25,10 @@ from distributed_neural_networks_amd.ops import _lib, cifar as cops  # noqa: E40
 
 # wide_store is a switch of the 32x32x16 conv2 path: it is compared with that path forced
 SWITCHES = {"wide_store": lambda v: _lib.lib().cifar_s0_set_mfma(0) or _lib.lib().cifar_s0_set_wide_store(v),
-            "mfma16": lambda v: _lib.lib().cifar_s0_set_mfma(v)}
-DEFAULTS = {"wide_store": lambda: 1, "mfma16": lambda: _lib.lib().cifar_s0_get_mfma()}
+            "mfma16": lambda v: _lib.lib().cifar_s0_set_mfma(v),
+            "conv1_k32": lambda v: _lib.lib().cifar_s0_set_conv1(v)}
+DEFAULTS = {"wide_store": lambda: 1, "mfma16": lambda: _lib.lib().cifar_s0_get_mfma(),
+            "conv1_k32": lambda: _lib.lib().cifar_s0_get_conv1()}
 
 
 def main():

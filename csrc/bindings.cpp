@@ -138,11 +138,14 @@ PYBIND11_MODULE(_dnn_hip, m) {
   });
   m.def("cifar_set_v4_pt", [](int pt) { return dnn_cifar_set_v4_pt(pt); });
   m.def("cifar_stage0_x3", [](u64 x, u64 out, u64 w1h, u64 w1l, u64 b1, u64 w2h, u64 w2l, u64 b2, int B, int grid,
-                              u64 st, int split_out) {
+                              u64 st, int split_out, u64 w1h32, u64 w1l32) {
     return dnn_cifar_stage0_x3(CFP(x), FP(out), CP(w1h), CP(w1l), CFP(b1), CP(w2h), CP(w2l), CFP(b2), B, grid,
-                               ST(st), split_out);
+                               ST(st), split_out, CP(w1h32), CP(w1l32));
   }, py::arg("x"), py::arg("out"), py::arg("w1h"), py::arg("w1l"), py::arg("b1"), py::arg("w2h"), py::arg("w2l"),
-        py::arg("b2"), py::arg("B"), py::arg("grid"), py::arg("st"), py::arg("split_out") = 0);
+        py::arg("b2"), py::arg("B"), py::arg("grid"), py::arg("st"), py::arg("split_out") = 0,
+        py::arg("w1h32") = 0, py::arg("w1l32") = 0);
+  m.def("cifar_s0_set_conv1", [](int v) { return dnn_cifar_s0_set_conv1(v); });
+  m.def("cifar_s0_get_conv1", []() { return dnn_cifar_s0_get_conv1(); });
   m.def("cifar_s0_set_wide_store", [](int on) { return dnn_cifar_s0_set_wide_store(on); });
   m.def("cifar_s0_set_mfma", [](int v) { return dnn_cifar_s0_set_mfma(v); });
   m.def("cifar_s0_get_mfma", []() { return dnn_cifar_s0_get_mfma(); });

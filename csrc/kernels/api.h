@@ -85,7 +85,10 @@ int dnn_cifar_stage0_v4(const float* x, void* out, const void* w1p, const float*
                         int B, int grid, hipStream_t st);
 int dnn_cifar_set_v4_pt(int pt);
 int dnn_cifar_stage0_x3(const float* x, float* out, const void* w1h, const void* w1l, const float* b1, const void* w2h,
-                        const void* w2l, const float* b2, int B, int grid, hipStream_t st, int split_out = 0);
+                        const void* w2l, const float* b2, int B, int grid, hipStream_t st, int split_out = 0,
+                        const void* w1h32 = nullptr, const void* w1l32 = nullptr);
+int dnn_cifar_s0_set_conv1(int v);
+int dnn_cifar_s0_get_conv1();
 int dnn_cifar_s0_set_wide_store(int on);
 int dnn_cifar_s0_set_mfma(int v);
 int dnn_cifar_s0_get_mfma();

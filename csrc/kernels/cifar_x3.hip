@@ -27,6 +27,33 @@
 //    on v_mfma_f32_16x16x32_bf16" below: 1728 of them per image at the same
 //    MFMA cycles, chunk XOR (2*Y & 3), 16-B stores); the 32x32x16 consumer
 //    stays compiled as the A/B's other arm (dnn_cifar_s0_set_mfma).
+//    conv1 on K = 32 (template parameter C1 = 1, dnn_cifar_s0_set_conv1; the
+//    K = 48 producer above stays compiled as the other arm): the zero fourth
+//    channel and the zero kx = 3 tap go, 32 tiles x 2 k-steps x 3 terms = 192
+//    conv1 MFMAs per image instead of 288 (33,792 matrix-pipe cycles per image
+//    with conv2 instead of 36,864).  LDS (113,408 B): the input double-buffered
+//    as hi/lo channel-packed planes [34 rows][112 bf16] (pitch 224 B = 56
+//    dwords): one zero element, then 34 pixels x 3 channels, halo included, so
+//    image pixel x sits at element 3x + 4 and four pixels are 24 B on an 8-B
+//    boundary (three ds_write_b64 per plane and thread; 16 contiguous lanes
+//    stage rows y and y + 2, 48 dwords = 16 banks apart: conflict-free).  Pixel
+//    x's 9-element window of one ky starts at element 3x + 1; the 4-B-aligned
+//    5-dword read that covers it starts at 3x (even x: [junk, v0..v8]) or 3x + 1
+//    (odd x: [v0..v8, junk]), and the junk element meets a zero weight, so an M
+//    tile holds pixels of one x parity and each parity has its own resident
+//    weight set [32 oc][32 k] (ops/cifar.py::_conv1_k32).  A tile is 4 rows x 8
+//    columns of one parity (lane: row l>>3 & 3, column index l & 7, K half
+//    h = l>>5); the even and the odd tile of the same 4 x 16 pixels run as one
+//    pair, and the 2x2 pool is the max over the two accumulators.  K order:
+//    half 0 holds dwords 0-3 of padded row 0 (k-step 0) and row 1 (k-step 1),
+//    half 1 dwords 0-3 of row 2 (k-step 0) and dword 4 of rows 0, 1, 2 plus a
+//    repeat of the last as filler (k-step 1); the last read of a row ends at
+//    element 103 of 112, inside the same plane.  All reads are 32-bit
+//    (ds_read2_b32; a 64- or 128-bit read at 4-B alignment would replay): each
+//    32-lane half reads 4 rows x 8 columns at 56 r + 3 c dwords, and 56 = 24
+//    (mod 32) is, with 8, the only pitch class for which {24 r + 3 c} are 32
+//    distinct banks (searched over all pitches >= 51 dwords).  The pooled conv1
+//    planes, their swizzle and the consumers are the same in both arms.
 //  * cifar_fc1_x3_kernel: fc1 + bias + ReLU on the fp32 boundary tensor, the
 //    split done in registers while staging A (no split copy in HBM): 256x256x32
 //    tiles, 8 waves of 128x64, per k32 step 3 x 32 mfma_f32_16x16x32_bf16 per
@@ -60,11 +87,26 @@ __device__ __forceinline__ int dpp_xor2(int v) { return __builtin_amdgcn_mov_dpp
 constexpr int XW = 40;                        // xin row pitch (pixels); HWC4 bf16 = 8 B/pixel
 constexpr int XPL = 34 * XW * 8;              // 10880: one input plane
 constexpr int A1PL = 18 * 18 * 64;            // 20736: one pooled-conv1 plane [18][18][32] bf16
-constexpr int A1_OFF = 4 * XPL;               // 43520
-constexpr int LDS_BYTES = A1_OFF + 4 * A1PL;  // 126464
+constexpr int XP32 = 224;                     // C1 = 1: xin row pitch in bytes (56 dwords, 103 bf16 used)
+constexpr int XPL32 = 34 * XP32;              // 7616: one channel-packed input plane
 
-__device__ __forceinline__ int xin_off(int k, int lo) { return ((k & 1) * 2 + lo) * XPL; }
-__device__ __forceinline__ int a1_off(int k, int lo) { return A1_OFF + ((k & 1) * 2 + lo) * A1PL; }
+// C1: conv1 producer path.  0: HWC4 planes, K = 48; 1: channel-packed planes, K = 32.
+template <int C1>
+__device__ __forceinline__ constexpr int xpl() {
+  return C1 ? XPL32 : XPL;
+}
+template <int C1>
+__device__ __forceinline__ constexpr int lds_bytes() {  // 126464 (C1 = 0), 113408 (C1 = 1)
+  return 4 * xpl<C1>() + 4 * A1PL;
+}
+template <int C1>
+__device__ __forceinline__ int xin_off(int k, int lo) {
+  return ((k & 1) * 2 + lo) * xpl<C1>();
+}
+template <int C1>
+__device__ __forceinline__ int a1_off(int k, int lo) {
+  return 4 * xpl<C1>() + ((k & 1) * 2 + lo) * A1PL;
+}
 
 // conv2 A-fragment immediate offset for k-step S (tap = S>>1, kx = tap % 3),
 // tile column I (tx2) and plane (LO): the lane/ky/parity part lives in the base.
@@ -208,11 +250,12 @@ using namespace x3;
 // C2: conv2 consumer path.  0: v_mfma_f32_32x32x16_bf16 (32x8-pixel M tiles);
 // 1: v_mfma_f32_16x16x32_bf16 (4x4-pixel M tiles, 16-B stores only), the default:
 // the same MFMA cycles, a higher clock held under load (docs/ARCHITECTURE.md §2).
-template <bool WIDE, bool SPLIT_OUT, int C2 = 0>
+template <bool WIDE, bool SPLIT_OUT, int C2 = 0, int C1 = 0>
 __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
     const float* __restrict__ x, float* __restrict__ out, const bf16_t* __restrict__ w1h,
     const bf16_t* __restrict__ w1l, const float* __restrict__ b1, const bf16_t* __restrict__ w2h,
     const bf16_t* __restrict__ w2l, const float* __restrict__ b2, int B) {
+  constexpr int LDS_BYTES = lds_bytes<C1>();
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -232,55 +275,15 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
   // producers hold conv1's split weights + the input prefetch, consumers the
   // 144 VGPRs of conv2's split weights.
   if (producer) {
-    bf16x8 w1hf[3], w1lf[3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      w1hf[s] = *reinterpret_cast<const bf16x8*>(w1h + r32 * 48 + s * 16 + h * 8);
-      w1lf[s] = *reinterpret_cast<const bf16x8*>(w1l + r32 * 48 + s * 16 + h * 8);
-    }
     const float bias = b1[r32];
-    resident_fence(w1hf);
-    resident_fence(w1lf);
     asm volatile("" ::"v"(bias));
-
-    float pf[4][3];
-    auto load_img = [&](int k) {
-      const float* xb = x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pf[i][c] = xb[c * 1024 + rt + 256 * i];
-    };
-    auto stage_img = [&](int k) {  // prefetch registers -> padded HWC4 hi / lo planes
-      char* xh = smem + xin_off(k, 0);
-      char* xl = smem + xin_off(k, 1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int p = rt + 256 * i, yy = p >> 5, xx = p & 31;
-        uint2 vh, vl;
-        split2(pf[i][0], pf[i][1], vh.x, vl.x);
-        split2(pf[i][2], 0.f, vh.y, vl.y);
-        const int o = ((yy + 1) * XW + xx + 1) * 8;
-        *reinterpret_cast<uint2*>(xh + o) = vh;
-        *reinterpret_cast<uint2*>(xl + o) = vl;
-      }
-    };
-    const int c1_lane = ((r32 >> 3) * XW + (r32 & 7) + 2 * h) * 8;
     const int q = ((r32 & 1) ? 2 : 0) + ((r32 & 2) ? 1 : 0);
     const int cb = r32 & ~3;
 
-    // bias + ReLU + 2x2 max-pool in registers (max(a)+b == max(a+b) exactly), quad-DPP
-    // gather of 4 channels of one pooled pixel per lane, hi/lo split, one 8-B store per plane
-    auto conv1_epi = [&](int t, const f32x16& acc, int k) {
-      const int ty = t >> 2, tx = t & 3;
-      float v[4];
-#pragma unroll
-      for (int qy = 0; qy < 2; ++qy)
-#pragma unroll
-        for (int qx = 0; qx < 2; ++qx) {
-          const int g0 = (2 * qy) * 4 + 2 * qx;
-          v[qy * 2 + qx] = fmaxf(fmax_nan(fmax_nan(acc[g0], acc[g0 + 1]), fmax_nan(acc[g0 + 4], acc[g0 + 5])) + bias, 0.f);
-        }
+    // v = bias + ReLU + 2x2 max-pool of the lane's 2x2 pooled pixels (Y0 + qy, X0 + qx) of
+    // channel r32: quad-DPP gather of 4 channels of one pooled pixel per lane, hi/lo split,
+    // one 8-B store per plane
+    auto conv1_store = [&](const float (&v)[4], int Y0, int X0, int k) {
       const bool odd = r32 & 1;
       const int s0 = __float_as_int(odd ? v[0] : v[2]), s1 = __float_as_int(odd ? v[1] : v[3]);
       const float r0 = __int_as_float(dpp_xor1(s0)), r1 = __int_as_float(dpp_xor1(s1));
@@ -301,59 +304,213 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       wh.y = hi2 ? mh : rch;
       wl.x = hi2 ? rcl : ml;
       wl.y = hi2 ? ml : rcl;
-      const int Y = 2 * ty + (q >> 1) + 1, X = 4 * tx + 2 * h + (q & 1) + 1;
+      const int Y = Y0 + (q >> 1), X = X0 + (q & 1);
       const int o = (Y * 18 + X) * 64 + ((((cb >> 3) ^ a1_swz<C2>(Y))) << 4) + (cb & 7) * 2;
-      *reinterpret_cast<uint2*>(smem + a1_off(k, 0) + o) = wh;
-      *reinterpret_cast<uint2*>(smem + a1_off(k, 1) + o) = wl;
+      *reinterpret_cast<uint2*>(smem + a1_off<C1>(k, 0) + o) = wh;
+      *reinterpret_cast<uint2*>(smem + a1_off<C1>(k, 1) + o) = wl;
     };
-    auto frag = [&](const char* p) {
-      const uint2 a = *reinterpret_cast<const uint2*>(p);
-      const uint2 b = *reinterpret_cast<const uint2*>(p + 8);
-      return __builtin_bit_cast(bf16x8, make_uint4(a.x, a.y, b.x, b.y));
-    };
-    // two conv1 tiles at once: all 24 A-fragment reads up front, two accumulation chains interleaved
-    auto conv1_pair = [&](int ta, int tb, int k) {
-      const char* xh = smem + xin_off(k, 0);
-      const int oa = c1_lane + ((4 * (ta >> 2)) * XW + 8 * (ta & 3)) * 8;
-      const int ob = c1_lane + ((4 * (tb >> 2)) * XW + 8 * (tb & 3)) * 8;
-      bf16x8 fah[3], fal[3], fbh[3], fbl[3];
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        fah[s] = frag(xh + oa + s * XW * 8);
-        fbh[s] = frag(xh + ob + s * XW * 8);
-        fal[s] = frag(xh + XPL + oa + s * XW * 8);
-        fbl[s] = frag(xh + XPL + ob + s * XW * 8);
-      }
-      f32x16 acca = {}, accb = {};
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[s], w1hf[s], acca, 0, 0, 0);
-        accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbh[s], w1hf[s], accb, 0, 0, 0);
-        acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[s], w1lf[s], acca, 0, 0, 0);
-        accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbh[s], w1lf[s], accb, 0, 0, 0);
-        acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[s], w1hf[s], acca, 0, 0, 0);
-        accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbl[s], w1hf[s], accb, 0, 0, 0);
-      }
-      conv1_epi(ta, acca, k);
-      conv1_epi(tb, accb, k);
-    };
-
-    if (n > 0) {
-      load_img(0);
-      stage_img(0);
-      if (n > 1) load_img(1);
-    }
-    __syncthreads();
-    for (int it = 0; it <= n; ++it) {
-      if (it < n) {
-#pragma unroll 1
-        for (int t = rw; t < 32; t += 8) conv1_pair(t, t + 4, it);
-        if (it + 1 < n) {
-          stage_img(it + 1);
-          if (it + 2 < n) load_img(it + 2);
-        }
+    // one barrier per image: conv1 of image it, then staging of image it+1 from the prefetch registers
+    auto produce = [&](auto&& load_img, auto&& stage_img, auto&& conv1_img) {
+      if (n > 0) {
+        load_img(0);
+        stage_img(0);
+        if (n > 1) load_img(1);
       }
       __syncthreads();
+      for (int it = 0; it <= n; ++it) {
+        if (it < n) {
+          conv1_img(it);
+          if (it + 1 < n) {
+            stage_img(it + 1);
+            if (it + 2 < n) load_img(it + 2);
+          }
+        }
+        __syncthreads();
+      }
+    };
+
+    if constexpr (C1 == 0) {
+      bf16x8 w1hf[3], w1lf[3];
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        w1hf[s] = *reinterpret_cast<const bf16x8*>(w1h + r32 * 48 + s * 16 + h * 8);
+        w1lf[s] = *reinterpret_cast<const bf16x8*>(w1l + r32 * 48 + s * 16 + h * 8);
+      }
+      resident_fence(w1hf);
+      resident_fence(w1lf);
+
+      float pf[4][3];
+      auto load_img = [&](int k) {
+        const float* xb = x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) pf[i][c] = xb[c * 1024 + rt + 256 * i];
+      };
+      auto stage_img = [&](int k) {  // prefetch registers -> padded HWC4 hi / lo planes
+        char* xh = smem + xin_off<C1>(k, 0);
+        char* xl = smem + xin_off<C1>(k, 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int p = rt + 256 * i, yy = p >> 5, xx = p & 31;
+          uint2 vh, vl;
+          split2(pf[i][0], pf[i][1], vh.x, vl.x);
+          split2(pf[i][2], 0.f, vh.y, vl.y);
+          const int o = ((yy + 1) * XW + xx + 1) * 8;
+          *reinterpret_cast<uint2*>(xh + o) = vh;
+          *reinterpret_cast<uint2*>(xl + o) = vl;
+        }
+      };
+      const int c1_lane = ((r32 >> 3) * XW + (r32 & 7) + 2 * h) * 8;
+
+      // bias + ReLU + 2x2 max-pool in registers (max(a)+b == max(a+b) exactly)
+      auto conv1_epi = [&](int t, const f32x16& acc, int k) {
+        const int ty = t >> 2, tx = t & 3;
+        float v[4];
+#pragma unroll
+        for (int qy = 0; qy < 2; ++qy)
+#pragma unroll
+          for (int qx = 0; qx < 2; ++qx) {
+            const int g0 = (2 * qy) * 4 + 2 * qx;
+            v[qy * 2 + qx] =
+                fmaxf(fmax_nan(fmax_nan(acc[g0], acc[g0 + 1]), fmax_nan(acc[g0 + 4], acc[g0 + 5])) + bias, 0.f);
+          }
+        conv1_store(v, 2 * ty + 1, 4 * tx + 2 * h + 1, k);
+      };
+      auto frag = [&](const char* p) {
+        const uint2 a = *reinterpret_cast<const uint2*>(p);
+        const uint2 b = *reinterpret_cast<const uint2*>(p + 8);
+        return __builtin_bit_cast(bf16x8, make_uint4(a.x, a.y, b.x, b.y));
+      };
+      // two conv1 tiles at once: all 24 A-fragment reads up front, two accumulation chains interleaved
+      auto conv1_pair = [&](int ta, int tb, int k) {
+        const char* xh = smem + xin_off<C1>(k, 0);
+        const int oa = c1_lane + ((4 * (ta >> 2)) * XW + 8 * (ta & 3)) * 8;
+        const int ob = c1_lane + ((4 * (tb >> 2)) * XW + 8 * (tb & 3)) * 8;
+        bf16x8 fah[3], fal[3], fbh[3], fbl[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+          fah[s] = frag(xh + oa + s * XW * 8);
+          fbh[s] = frag(xh + ob + s * XW * 8);
+          fal[s] = frag(xh + XPL + oa + s * XW * 8);
+          fbl[s] = frag(xh + XPL + ob + s * XW * 8);
+        }
+        f32x16 acca = {}, accb = {};
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+          acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[s], w1hf[s], acca, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbh[s], w1hf[s], accb, 0, 0, 0);
+          acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[s], w1lf[s], acca, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbh[s], w1lf[s], accb, 0, 0, 0);
+          acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[s], w1hf[s], acca, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbl[s], w1hf[s], accb, 0, 0, 0);
+        }
+        conv1_epi(ta, acca, k);
+        conv1_epi(tb, accb, k);
+      };
+      produce(load_img, stage_img, [&](int it) {
+#pragma unroll 1
+        for (int t = rw; t < 32; t += 8) conv1_pair(t, t + 4, it);
+      });
+    } else {
+      // conv1 with the 27 taps in K = 32 (see "conv1 on K = 32" in the header): per x parity a
+      // resident weight set [par][k-step], B-operand k = 16*s + 8*h + 0..7
+      bf16x8 w1hf[2][2], w1lf[2][2];
+#pragma unroll
+      for (int par = 0; par < 2; ++par)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          w1hf[par][s] = *reinterpret_cast<const bf16x8*>(w1h + par * 1024 + r32 * 32 + s * 16 + h * 8);
+          w1lf[par][s] = *reinterpret_cast<const bf16x8*>(w1l + par * 1024 + r32 * 32 + s * 16 + h * 8);
+        }
+      resident_fence(w1hf[0]);
+      resident_fence(w1hf[1]);
+      resident_fence(w1lf[0]);
+      resident_fence(w1lf[1]);
+
+      // a thread stages pixels 4j..4j+3 of one row: 12 contiguous bf16 per plane from element
+      // 12j + 4 (8-B aligned).  16 contiguous lanes take rows y and y + 2 (24 dwords mod 32
+      // apart would collide, 48 do not): conflict-free ds_write_b64
+      const int sj = rt & 7, r5 = rt >> 3;
+      const int sy = (r5 & ~3) | ((r5 & 1) << 1) | ((r5 >> 1) & 1);
+      float4 pf[3];
+      auto load_img = [&](int k) {
+        const float* xb = x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072 + sy * 32 + sj * 4;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pf[c] = *reinterpret_cast<const float4*>(xb + c * 1024);
+      };
+      auto stage_img = [&](int k) {  // prefetch registers -> padded channel-packed hi / lo planes
+        const int o = (sy + 1) * XP32 + 8 + 24 * sj;
+        char* xh = smem + xin_off<C1>(k, 0) + o;
+        char* xl = smem + xin_off<C1>(k, 1) + o;
+        uint2 vh[3], vl[3];
+        split2(pf[0].x, pf[1].x, vh[0].x, vl[0].x);
+        split2(pf[2].x, pf[0].y, vh[0].y, vl[0].y);
+        split2(pf[1].y, pf[2].y, vh[1].x, vl[1].x);
+        split2(pf[0].z, pf[1].z, vh[1].y, vl[1].y);
+        split2(pf[2].z, pf[0].w, vh[2].x, vl[2].x);
+        split2(pf[1].w, pf[2].w, vh[2].y, vl[2].y);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          *reinterpret_cast<uint2*>(xh + 8 * i) = vh[i];
+          *reinterpret_cast<uint2*>(xl + 8 * i) = vl[i];
+        }
+      };
+      // lane (pixel row rr, column index c of the tile; K half h): k-step 0 reads dwords 0-3
+      // of padded row rr + 2h, k-step 1 dwords 0-3 of row rr + 1 (h = 0) or dword 4 of rows
+      // rr, rr + 1, rr + 2 and a repeat of the last as filler (h = 1)
+      const int rr = r32 >> 3, cc = r32 & 7;
+      const int l0 = (rr + 2 * h) * XP32 + 12 * cc;
+      int l1[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        l1[i] = h ? (rr + (i < 2 ? i : 2)) * XP32 + 12 * cc + 16 : (rr + 1) * XP32 + 12 * cc + 4 * i;
+      auto ld32 = [&](const char* p) { return *reinterpret_cast<const uint32_t*>(p); };
+      // the even and the odd tile of 4 rows x 16 columns: 32 dword reads up front, two
+      // accumulation chains interleaved, the 2x2 pool across the two accumulators
+      auto conv1_pair = [&](int tp, int k) {
+        const int ty = tp >> 1, tx2 = tp & 1;
+        const char* xh = smem + xin_off<C1>(k, 0) + 4 * ty * XP32 + 96 * tx2;
+        bf16x8 f[2][2][2];  // [x parity][hi, lo][k-step]
+#pragma unroll
+        for (int par = 0; par < 2; ++par)
+#pragma unroll
+          for (int pl = 0; pl < 2; ++pl) {
+            const char* p = xh + pl * XPL32 + 8 * par;
+            f[par][pl][0] = __builtin_bit_cast(
+                bf16x8, make_uint4(ld32(p + l0), ld32(p + l0 + 4), ld32(p + l0 + 8), ld32(p + l0 + 12)));
+            f[par][pl][1] = __builtin_bit_cast(
+                bf16x8, make_uint4(ld32(p + l1[0]), ld32(p + l1[1]), ld32(p + l1[2]), ld32(p + l1[3])));
+          }
+        f32x16 acca = {}, accb = {};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[0][0][s], w1hf[0][s], acca, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[1][0][s], w1hf[1][s], accb, 0, 0, 0);
+          acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[0][0][s], w1lf[0][s], acca, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[1][0][s], w1lf[1][s], accb, 0, 0, 0);
+          acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[0][1][s], w1hf[0][s], acca, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[1][1][s], w1hf[1][s], accb, 0, 0, 0);
+        }
+        // accumulator g of both tiles: pixel row 2*qy + ((g >> 2) & 1), column index (g & 3) + 4h
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          float v[4];
+#pragma unroll
+          for (int qy = 0; qy < 2; ++qy)
+#pragma unroll
+            for (int qx = 0; qx < 2; ++qx) {
+              const int g = 8 * qy + 2 * e + qx;
+              v[qy * 2 + qx] =
+                  fmaxf(fmax_nan(fmax_nan(acca[g], accb[g]), fmax_nan(acca[g + 4], accb[g + 4])) + bias, 0.f);
+            }
+          conv1_store(v, 2 * ty + 1, 8 * tx2 + 4 * h + 2 * e + 1, k);
+        }
+      };
+      produce(load_img, stage_img, [&](int it) {
+#pragma unroll 1
+        for (int tp = rw; tp < 16; tp += 4) conv1_pair(tp, it);
+      });
     }
   } else if constexpr (C2 != 0) {
     const int m = lane & 15, q16 = lane >> 4, y1 = q16 >> 1, x1 = q16 & 1;
@@ -381,7 +538,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
 
     auto conv2_img = [&](int k) {  // conv2 + bias + ReLU + pool of image k -> out
       float* img = out + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 4096;
-      const uint32_t plane = (uint32_t)(uintptr_t)(smem + a1_off(k, 0));
+      const uint32_t plane = (uint32_t)(uintptr_t)(smem + a1_off<C1>(k, 0));
 #pragma unroll 1
       for (int p = 0; p < 2; ++p) {
         const int ty2 = (rw >> 1) * 2 + p;
@@ -428,7 +585,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
 
     auto conv2_img = [&](int k) {  // conv2 + bias + ReLU + pool of image k -> out (fp32, NCHW flatten)
       float* ob = out + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 4096 + oc2 * 64;
-      const uint32_t plane = (uint32_t)(uintptr_t)(smem + a1_off(k, 0));
+      const uint32_t plane = (uint32_t)(uintptr_t)(smem + a1_off<C1>(k, 0));
 #pragma unroll 1
       for (int p = 0; p < 2; ++p) {
         const int ty2 = (rw >> 1) * 2 + p;
@@ -987,30 +1144,48 @@ extern "C" int dnn_cifar_s0_set_wide_store(int on) {
   return 0;
 }
 
-template <bool SPLIT_OUT>
+// conv1 K packing: 1 = K = 32 on channel-packed planes (default; every interleaved round faster than
+// K = 48, profiles/cifar_conv1_k32_ab.jsonl), 0 = K = 48 on HWC4 planes (the A/B's other arm)
+static int g_s0_conv1 = 1;
+
+extern "C" int dnn_cifar_s0_set_conv1(int v) {
+  if (v < 0 || v > 1) return 1;
+  g_s0_conv1 = v;
+  return 0;
+}
+
+extern "C" int dnn_cifar_s0_get_conv1() { return g_s0_conv1; }
+
+template <bool SPLIT_OUT, int C1>
 static int launch_stage0_x3(const float* x, float* out, const void* w1h, const void* w1l, const float* b1,
                             const void* w2h, const void* w2l, const float* b2, int B, int grid, hipStream_t st) {
   if (g_s0_mfma == 1)
-    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT, 1>), dim3(grid), dim3(512), 0, st, x, out,
+    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT, 1, C1>), dim3(grid), dim3(512), 0, st, x, out,
                        (const bf16_t*)w1h, (const bf16_t*)w1l, b1, (const bf16_t*)w2h, (const bf16_t*)w2l, b2, B);
   else if (g_s0_wide_store)
-    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT>), dim3(grid), dim3(512), 0, st, x, out,
+    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT, 0, C1>), dim3(grid), dim3(512), 0, st, x, out,
                        (const bf16_t*)w1h, (const bf16_t*)w1l, b1, (const bf16_t*)w2h, (const bf16_t*)w2l, b2, B);
   else
-    hipLaunchKernelGGL((cifar_stage0_x3_kernel<false, SPLIT_OUT>), dim3(grid), dim3(512), 0, st, x, out,
+    hipLaunchKernelGGL((cifar_stage0_x3_kernel<false, SPLIT_OUT, 0, C1>), dim3(grid), dim3(512), 0, st, x, out,
                        (const bf16_t*)w1h, (const bf16_t*)w1l, b1, (const bf16_t*)w2h, (const bf16_t*)w2l, b2, B);
   return (int)hipGetLastError();
 }
 
 // split_out = 1: the (B,4096) boundary in the blocked hi/lo encoding, else fp32.
+// w1h / w1l: conv1 [32][48] (K = 48 arm); w1h32 / w1l32: conv1 [2][32][32] (K = 32 arm, required by it).
 extern "C" int dnn_cifar_stage0_x3(const float* x, float* out, const void* w1h, const void* w1l, const float* b1,
                                    const void* w2h, const void* w2l, const float* b2, int B, int grid,
-                                   hipStream_t st, int split_out) {
+                                   hipStream_t st, int split_out, const void* w1h32, const void* w1l32) {
   if (B <= 0) return 0;
   if (grid <= 0) grid = 256;
   if (grid > B) grid = B;
-  return split_out ? launch_stage0_x3<true>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st)
-                   : launch_stage0_x3<false>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st);
+  if (g_s0_conv1 == 1) {
+    if (!w1h32 || !w1l32) return -1;
+    return split_out ? launch_stage0_x3<true, 1>(x, out, w1h32, w1l32, b1, w2h, w2l, b2, B, grid, st)
+                     : launch_stage0_x3<false, 1>(x, out, w1h32, w1l32, b1, w2h, w2l, b2, B, grid, st);
+  }
+  return split_out ? launch_stage0_x3<true, 0>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st)
+                   : launch_stage0_x3<false, 0>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st);
 }
 
 // fc1 k-loop schedule: 0 = lockstep, 1 = staggered wave groups (the A/B's two arms, bitwise-equal outputs)

@@ -26,7 +26,10 @@ fp32 modules to the device):
 
 Weight layouts:
 
-* conv1 ``(32,3,3,3)`` -> ``[32][48]`` with ``k = ky*16 + kx*4 + c`` (kx<3, c<3 real);
+* conv1 ``(32,3,3,3)`` -> ``[32][48]`` with ``k = ky*16 + kx*4 + c`` (kx<3, c<3 real): the
+  bf16 kernel and the fp32 kernel's ``k48`` arm; and, for the fp32 kernel's default ``k32`` arm
+  (``STAGE0_CONV1``), ``[2 x parity][32][32]`` with ``k = conv1_k32_slot(ky, p + kx*3 + c)``,
+  p = 1 for even x and 0 for odd x, every other slot zero (``_conv1_k32``);
 * conv2 ``(64,32,3,3)`` -> ``[64][288]`` with ``k = (ky*3+kx)*32 + c`` (HWC activation image);
 * fc1 ``[512][4096]`` (K-contiguous for the GEMM), fc2 ``(10,512)`` -> ``[16][512]``
   zero-padded to one MFMA N-tile.  Biases are fp32.
@@ -59,6 +62,33 @@ def _conv1_k48(sd) -> torch.Tensor:
     return w.reshape(32, 48)
 
 
+def conv1_k32_slot(ky: int, e: int) -> int:
+    """K index of element ``e`` (0..9) of the 5-dword read of padded input row
+    ``ky`` in the K = 32 conv1 (``cifar_x3.hip``, "conv1 on K = 32"): the MFMA's
+    k is ``16*step + 8*half + 0..7``; lane half 0 holds dwords 0-3 of rows 0
+    (step 0) and 1 (step 1), half 1 dwords 0-3 of row 2 (step 0) and dword 4 of
+    rows 0, 1, 2 (step 1).  K slots 30 and 31 are filler."""
+    if e < 8:
+        return (0, 16, 8)[ky] + e
+    return 24 + 2 * ky + (e - 8)
+
+
+def _conv1_k32(sd) -> torch.Tensor:
+    """conv1 ``(32,3,3,3)`` -> ``[2 x parity][32 oc][32 k]``.  An input row is
+    one zero element, then 34 pixels x 3 channels; pixel x's 9-element window of
+    one ky starts at element 3x + 1, and the 4-byte-aligned 10-element read that
+    covers it starts at 3x (even x: window at e = 1..9, e = 0 junk) or 3x + 1
+    (odd x: window at e = 0..8, e = 9 junk).  Junk and filler slots stay zero."""
+    w = sd["conv1.weight"].float()  # (oc, c, ky, kx)
+    out = torch.zeros(2, 32, 32)
+    for par in range(2):
+        for ky in range(3):
+            for kx in range(3):
+                for c in range(3):
+                    out[par, :, conv1_k32_slot(ky, (1 - par) + kx * 3 + c)] = w[:, c, ky, kx]
+    return out
+
+
 def _conv2_k288(sd) -> torch.Tensor:
     return sd["conv2.weight"].float().permute(0, 2, 3, 1).reshape(64, 288)  # (oc, ky, kx, c)
 
@@ -80,6 +110,8 @@ class CifarStage0Weights:
     w1l: torch.Tensor = None
     w2h: torch.Tensor = None
     w2l: torch.Tensor = None
+    w1h32: torch.Tensor = None  # fp32 path: conv1 in the K = 32 packing [2][32][32]
+    w1l32: torch.Tensor = None
 
 
 @dataclass
@@ -111,8 +143,10 @@ def pack_stage0(sd: Dict[str, torch.Tensor], device, precision: str = "fp32") ->
                                   w1=w1.to(device=device, dtype=torch.bfloat16).contiguous(),
                                   w2=w2.to(device=device, dtype=torch.bfloat16).contiguous())
     (w1h, w1l), (w2h, w2l) = split_bf16(w1), split_bf16(w2)
+    w1h32, w1l32 = split_bf16(_conv1_k32(sd))
     dv = lambda t: t.to(device).contiguous()  # noqa: E731
-    return CifarStage0Weights("fp32", b1, b2, w1h=dv(w1h), w1l=dv(w1l), w2h=dv(w2h), w2l=dv(w2l))
+    return CifarStage0Weights("fp32", b1, b2, w1h=dv(w1h), w1l=dv(w1l), w2h=dv(w2h), w2l=dv(w2l),
+                              w1h32=dv(w1h32), w1l32=dv(w1l32))
 
 
 def pack_head(sd: Dict[str, torch.Tensor], device, fc1: bool = True, fc2: bool = True,
@@ -167,6 +201,18 @@ def set_stage0_mfma(shape) -> int:
     v = STAGE0_MFMA[shape] if isinstance(shape, str) else int(shape)
     prev = lib().cifar_s0_get_mfma()
     check(lib().cifar_s0_set_mfma(v), "cifar_s0_set_mfma")
+    return prev
+
+
+STAGE0_CONV1 = {"k48": 0, "k32": 1}  # compiled conv1 producer paths (fp32); 1 is the default
+
+
+def set_stage0_conv1(packing) -> int:
+    """Select the K packing of the fp32 stage-0 conv1 producer (a key or value
+    of ``STAGE0_CONV1``); returns the previous setting so callers can restore it."""
+    v = STAGE0_CONV1[packing] if isinstance(packing, str) else int(packing)
+    prev = lib().cifar_s0_get_conv1()
+    check(lib().cifar_s0_set_conv1(v), "cifar_s0_set_conv1")
     return prev
 
 
@@ -228,7 +274,8 @@ def stage0_forward(x: torch.Tensor, w: CifarStage0Weights, out: Optional[torch.T
         raise ValueError("stage0: bad output buffer")
     if w.precision == "fp32":
         check(lib().cifar_stage0_x3(ptr(x), ptr(out), ptr(w.w1h), ptr(w.w1l), ptr(w.b1), ptr(w.w2h), ptr(w.w2l),
-                                    ptr(w.b2), B, grid, stream_ptr(), split), "cifar_stage0_x3")
+                                    ptr(w.b2), B, grid, stream_ptr(), split, ptr(w.w1h32), ptr(w.w1l32)),
+              "cifar_stage0_x3")
     else:
         check(lib().cifar_stage0_v4(ptr(x), ptr(out), ptr(w.w1), ptr(w.b1), ptr(w.w2), ptr(w.b2), B, grid,
                                     stream_ptr()), "cifar_stage0_v4")

@@ -6,11 +6,12 @@
 Without ``--switch``: split3 + K-concat bf16 GEMM vs the fused cifar_fc1_x3
 kernel (same math, same weights).
 
-``--switch sched``: the two k-loop schedules of the fused kernel (0 lockstep,
-1 staggered), interleaved rounds in one process (box-to-box clock differences
-cancel), each round one replay of a HIP graph of ``iters`` launches.  Every
-round is printed; an arm wins only if every one of its rounds is faster than
-every round of the other.  The two outputs must be bitwise equal.
+``--switch sched``: every k-loop arm of the fused kernel (``FC1_SCHED``: 0
+lockstep, 1 staggered, 2 lean), interleaved rounds in one process (box-to-box
+clock differences cancel), each round one replay of a HIP graph of ``iters``
+launches.  Every round is printed, with median and range per arm; an arm beats
+another only if every one of its rounds is faster than every round of the
+other.  All outputs must be bitwise equal.
 """
 import argparse
 import json
@@ -75,8 +76,8 @@ def sched(a):
     boundary = "split" if a.split_in else "fp32"
     if a.split_in:
         h = cops.encode_boundary(h)
-    arms = (0, 1)
     names = {v: k for k, v in cops.FC1_SCHED.items()}
+    arms = tuple(sorted(names))
     outs = {v: torch.empty(B, 512, device=dev) for v in arms}
     default = cops.set_fc1_sched(0)
     graphs = {}
@@ -104,15 +105,16 @@ def sched(a):
             torch.cuda.synchronize()
             times[v].append(e0.elapsed_time(e1) / a.iters)
             print(f"round {r} {names[v]}: {times[v][-1]:.4f} ms", flush=True)
-    equal = torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
+    equal = all(torch.equal(outs[arms[0]].view(torch.int32), outs[v].view(torch.int32)) for v in arms[1:])
     print(json.dumps({"switch": "sched", "B": B, "iters": a.iters, "split_in": a.split_in,
                       "default": names[default],
                       **{f"{names[v]}_ms": round(sorted(t)[len(t) // 2], 4) for v, t in times.items()},
+                      **{f"{names[v]}_range_ms": [round(min(t), 4), round(max(t), 4)] for v, t in times.items()},
                       **{f"{names[v]}_rounds_ms": [round(t_, 4) for t_ in t] for v, t in times.items()},
-                      "every_round_of_staggered_faster": max(times[1]) < min(times[0]),
-                      "every_round_of_lockstep_faster": max(times[0]) < min(times[1]),
+                      **{f"every_round_of_{names[x]}_faster_than_{names[y]}": max(times[x]) < min(times[y])
+                         for x in arms for y in arms if x != y},
                       "outputs_bitwise_equal": equal}), flush=True)
-    assert equal, "the two schedules' outputs differ"
+    assert equal, "the arms' outputs differ"
 
 
 def main():

@@ -58,10 +58,13 @@
 //    split done in registers while staging A (no split copy in HBM): 256x256x32
 //    tiles, 8 waves of 128x64, per k32 step 3 x 32 mfma_f32_16x16x32_bf16 per
 //    wave (A_hi W_hi + A_hi W_lo + A_lo W_hi) on 24 conflict-free ds_read_b128.
-//    By default waves 0-3 and 4-7 run half a k-step apart, so each SIMD pairs a
-//    wave issuing MFMAs with one reading, splitting and restaging ("STAG"
-//    below); the lockstep loop stays compiled as the A/B's other arm
-//    (dnn_cifar_fc1_set_sched).
+//    Waves 0-3 and 4-7 run half a k-step apart, so each SIMD pairs a wave
+//    issuing MFMAs with one reading, splitting and restaging ("STAG" below).
+//    The default arm is "LEAN": that schedule with the packed split
+//    (split2<true>) and all global addressing through buffer descriptors, 51
+//    non-MFMA vector instructions per k-step instead of 207; the staggered and
+//    the lockstep loops stay compiled as the A/B's other arms, on the code they
+//    had (dnn_cifar_fc1_set_sched: 0 lockstep, 1 staggered, 2 lean).
 //  * cifar_split3_kernel: fp32 (B,K) -> bf16 (B,3K) = [hi | hi | lo], the A
 //    operand of the small-batch fc1 (one skinny bf16 GEMM over K' = 3K against
 //    W' = [W_hi | W_lo | W_hi]) when the 256^2 tiles cannot fill the chip.
@@ -74,11 +77,49 @@
 namespace dnn {
 namespace x3 {
 
-// 2 floats -> packed bf16 hi pair and lo pair (element a in the low half)
+// 2 floats -> packed bf16 hi pair and lo pair (element a in the low half).
+// PK: both conversions as one v_cvt_pk_bf16_f32 per pair (6 VALU per pair
+// instead of ~11.5, bitwise the same values); the empty asm keeps the two
+// subtracts scalar (SLP would pack them into v_pk_add_f32, which costs more
+// than it saves beside MFMAs).  PK = false is the form the lockstep and
+// staggered fc1 arms and the head kernel keep: their code is unchanged.
+template <bool PK>
 __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = pack2bf(a, b);
-  const float ah = __uint_as_float(hi << 16), bh = __uint_as_float(hi & 0xffff0000u);
-  lo = pack2bf(a - ah, b - bh);
+  if constexpr (PK) {
+    hi = pack2bf_pk(a, b);
+    const float ah = __uint_as_float(hi << 16), bh = __uint_as_float(hi & 0xffff0000u);
+    float da = a - ah;
+    const float db = b - bh;
+    asm("" : "+v"(da));
+    lo = pack2bf_pk(da, db);
+  } else {
+    hi = pack2bf(a, b);
+    const float ah = __uint_as_float(hi << 16), bh = __uint_as_float(hi & 0xffff0000u);
+    lo = pack2bf(a - ah, b - bh);
+  }
+}
+
+// Raw-buffer loads of 16 B per lane: the address is the descriptor's wave-uniform
+// base + the lane's 32-bit voff + the scalar soff, with no per-lane 64-bit address
+// arithmetic.  The range check drops a lane whose voff + 16 passes ``bytes``: it
+// reads as 0 and touches no memory.  Do not count on soff being checked: put
+// whatever can leave the allocation into base / bytes or into voff.
+// base and bytes must be wave-uniform SGPR values, or every load gets a waterfall
+// loop.  Device pass only: the host has no buffer resource type.
+__device__ __forceinline__ float4 buf_load16(const void* base, int bytes, int voff, int soff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
+  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0));
+#else
+  return float4{};
+#endif
+}
+// the same load as LDS DMA (glds16's layout: lane l lands at lds_wave_base + 16 l)
+__device__ __forceinline__ void buf_glds16(const void* base, int bytes, int voff, int soff, void* lds_wave_base) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_AS void*)lds_wave_base, 16, voff, soff, 0, 0);
+#endif
 }
 
 __device__ __forceinline__ int dpp_xor1(int v) { return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false); }
@@ -231,8 +272,8 @@ __device__ __forceinline__ void m16_epilogue(const f32x4 (&acc)[4][2], float bia
   const auto s1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[1]), __float_as_uint(v[3]), false, false);
   if constexpr (SPLIT_OUT) {  // k = oc*64 + PY*8 + 4*x1 + 0..3
     uint2 hi, lo;
-    split2(__uint_as_float(s0[0]), __uint_as_float(s0[1]), hi.x, lo.x);
-    split2(__uint_as_float(s1[0]), __uint_as_float(s1[1]), hi.y, lo.y);
+    split2<true>(__uint_as_float(s0[0]), __uint_as_float(s0[1]), hi.x, lo.x);
+    split2<true>(__uint_as_float(s1[0]), __uint_as_float(s1[1]), hi.y, lo.y);
     char* bp = reinterpret_cast<char*>(img) + (oc * 2 + (PY >> 2)) * 128 + ((PY & 3) * 8 + 4 * x1) * 2;
     *reinterpret_cast<uint2*>(bp) = hi;
     *reinterpret_cast<uint2*>(bp + 64) = lo;
@@ -289,11 +330,11 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       const float r0 = __int_as_float(dpp_xor1(s0)), r1 = __int_as_float(dpp_xor1(s1));
       uint32_t u0h, u0l, u1h, u1l;
       if (!odd) {
-        split2(v[0], r0, u0h, u0l);
-        split2(v[1], r1, u1h, u1l);
+        split2<true>(v[0], r0, u0h, u0l);
+        split2<true>(v[1], r1, u1h, u1l);
       } else {
-        split2(r0, v[2], u0h, u0l);
-        split2(r1, v[3], u1h, u1l);
+        split2<true>(r0, v[2], u0h, u0l);
+        split2<true>(r1, v[3], u1h, u1l);
       }
       const bool hi2 = r32 & 2;
       const uint32_t rch = (uint32_t)dpp_xor2((int)(hi2 ? u0h : u1h));
@@ -354,8 +395,8 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
         for (int i = 0; i < 4; ++i) {
           const int p = rt + 256 * i, yy = p >> 5, xx = p & 31;
           uint2 vh, vl;
-          split2(pf[i][0], pf[i][1], vh.x, vl.x);
-          split2(pf[i][2], 0.f, vh.y, vl.y);
+          split2<true>(pf[i][0], pf[i][1], vh.x, vl.x);
+          split2<true>(pf[i][2], 0.f, vh.y, vl.y);
           const int o = ((yy + 1) * XW + xx + 1) * 8;
           *reinterpret_cast<uint2*>(xh + o) = vh;
           *reinterpret_cast<uint2*>(xl + o) = vl;
@@ -444,12 +485,12 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
         char* xh = smem + xin_off<C1>(k, 0) + o;
         char* xl = smem + xin_off<C1>(k, 1) + o;
         uint2 vh[3], vl[3];
-        split2(pf[0].x, pf[1].x, vh[0].x, vl[0].x);
-        split2(pf[2].x, pf[0].y, vh[0].y, vl[0].y);
-        split2(pf[1].y, pf[2].y, vh[1].x, vl[1].x);
-        split2(pf[0].z, pf[1].z, vh[1].y, vl[1].y);
-        split2(pf[2].z, pf[0].w, vh[2].x, vl[2].x);
-        split2(pf[1].w, pf[2].w, vh[2].y, vl[2].y);
+        split2<true>(pf[0].x, pf[1].x, vh[0].x, vl[0].x);
+        split2<true>(pf[2].x, pf[0].y, vh[0].y, vl[0].y);
+        split2<true>(pf[1].y, pf[2].y, vh[1].x, vl[1].x);
+        split2<true>(pf[0].z, pf[1].z, vh[1].y, vl[1].y);
+        split2<true>(pf[2].z, pf[0].w, vh[2].x, vl[2].x);
+        split2<true>(pf[1].w, pf[2].w, vh[2].y, vl[2].y);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
           *reinterpret_cast<uint2*>(xh + 8 * i) = vh[i];
@@ -621,8 +662,8 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
             const int PY = 2 * ty2 + qy;
             if constexpr (SPLIT_OUT) {  // k = oc2*64 + PY*8 + 4h + 0..3: one 8-B hi and one 8-B lo store
               uint2 hi, lo;
-              split2(__uint_as_float(sx[0]), __uint_as_float(sy[0]), hi.x, lo.x);
-              split2(__uint_as_float(sx[1]), __uint_as_float(sy[1]), hi.y, lo.y);
+              split2<true>(__uint_as_float(sx[0]), __uint_as_float(sy[0]), hi.x, lo.x);
+              split2<true>(__uint_as_float(sx[1]), __uint_as_float(sy[1]), hi.y, lo.y);
               char* bp = reinterpret_cast<char*>(ob - oc2 * 64) + (oc2 * 2 + (PY >> 2)) * 128 + ((PY & 3) * 8 + 4 * h) * 2;
               *reinterpret_cast<uint2*>(bp) = hi;
               *reinterpret_cast<uint2*>(bp + 64) = lo;
@@ -643,7 +684,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
             const int PY = 2 * ty2 + qy, PX = 4 * i + 2 * h;
             if constexpr (SPLIT_OUT) {
               uint32_t hi, lo;
-              split2(pv.x, pv.y, hi, lo);
+              split2<true>(pv.x, pv.y, hi, lo);
               char* bp = reinterpret_cast<char*>(ob - oc2 * 64) + (oc2 * 2 + (PY >> 2)) * 128 + ((PY & 3) * 8 + PX) * 2;
               *reinterpret_cast<uint32_t*>(bp) = hi;
               *reinterpret_cast<uint32_t*>(bp + 64) = lo;
@@ -735,7 +776,29 @@ __device__ __forceinline__ void f1_tile_coords(int logical, int ntm, int ntn, in
 // nk >= 1: group 0 ends with the barrier after its last MFMAs and goes to its
 // epilogue while group 1 runs its last MFMA segment.  Each accumulator sees the
 // same MFMAs in the same order as lockstep: the outputs are bitwise equal.
-template <bool SPLIT_IN, bool STAG = false>
+//
+// LEAN (with STAG): the same segments, barriers, counted vmcnt and MFMA order,
+// with what a load segment issues next to its partner's MFMAs cut to the split
+// itself.  The staggered arm rebuilds every row pointer and LDS offset per
+// segment (64-bit per-lane arithmetic, ~85 VALU per k-step) because it has no
+// VGPRs to keep them; none of it depends on the k-step except through a
+// wave-uniform offset.  Here A, W and (SPLIT_IN) the blocked A go through buffer
+// descriptors built from block-uniform values (buf_load16 / buf_glds16): one
+// loop-invariant 32-bit lane offset per stream, the k-step, the hi / lo half
+// and the 16-row piece in the scalar offset.  The A ds_write address and the
+// A / W fragment ds_read_b128 addresses are one VGPR base each plus immediates;
+// the buffer toggle is 65536 B, one past the largest ds immediate, so it is one
+// v_add per base and segment.  Five persistent VGPRs replace the recomputation
+// (256 VGPRs, no scratch, as before).  Rows past M: instead of the clamp to
+// row M - 1 the descriptors end with the tile's last valid row (fp32 A: four
+// descriptors of 64 rows, one per piece, since the piece offset must not ride
+// in the scalar offset, which the check may not cover; blocked A: one descriptor, the row in the
+// lane offset), so such a row is dropped by the range check, reads as zero and
+// is never stored.  split2<true> converts each pair with one
+// v_cvt_pk_bf16_f32: the same instruction and rounding on the same values, so
+// the outputs are bitwise those of the other arms.  Measured in
+// profiles/cifar_lean_after.md: fc1 0.646 -> 0.572 ms interleaved, every round.
+template <bool SPLIT_IN, bool STAG = false, bool LEAN = false>
 __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __restrict__ A, int lda,
                                                               const bf16_t* __restrict__ Wh,
                                                               const bf16_t* __restrict__ Wl, int ldw,
@@ -764,7 +827,55 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
   // registers + 16 of A in flight leave 16 for everything else at 2 waves/SIMD.
   int ltid = tid;
   float4 ar[4];
+  // LEAN addressing (see above the kernel): descriptors from block-uniform
+  // values, one 32-bit lane offset per stream, one LDS base per access kind.
+  static_assert(!LEAN || STAG, "the lean arm is the staggered schedule");
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  // fp32 A, piece k (rows m0 + 64 k ..+63): the records end with row M - 1, so
+  // a row past M is dropped by the range check (reads as 0, is never stored)
+  // (readfirstlane: the clamp compiles to v_med3_i32, and a record count in a
+  // VGPR would put a waterfall loop around every load)
+  int a_rows[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a_rows[k] = __builtin_amdgcn_readfirstlane(max(min(M - m0 - 64 * k, 64), 0));
+  // blocked A (SPLIT_IN): the tile's rows in one descriptor, the row in the lane offset
+  const float* const a_tile = A + (size_t)m0 * lda;
+  const int a_tile_bytes = min(M - m0, F1_T) * lda * 4;
+  // DMA lane offset: row wave * 32 + (lane >> 2) of pitch ld bytes, swizzled 16-B chunk (piece j: + 16 rows)
+  auto dma_voff = [&](int ld_bytes) {
+    return (wave * 32 + (lane >> 2)) * ld_bytes + (((lane & 3) ^ ((lane >> 4) & 2)) << 4);
+  };
+  int a_voff = 0, a_voff1 = 0, w_voff = 0;
+  LDS_AS char* aw_base = nullptr;
+  LDS_AS char* fa_base = nullptr;
+  LDS_AS char* fw_base = nullptr;
+  if constexpr (LEAN) {
+    LDS_AS char* const lds = (LDS_AS char*)smem;
+    const int fr = lane & 15, fc = lane >> 4;
+    const int fo = fr * 64 + ((fc ^ ((fr >> 2) & 2)) << 4);  // f1_frag's row fr, chunk fc
+    fa_base = lds + (wave >> 2) * 128 * 64 + fo;
+    fw_base = lds + 2 * F1_PLANE + (wave & 3) * 64 * 64 + fo;
+    w_voff = dma_voff(ldw * 2);
+    if constexpr (SPLIT_IN) {
+      a_voff = dma_voff(lda * 4);
+      a_voff1 = a_voff + 16 * lda * 4;
+      asm volatile("" : "+v"(a_voff1));
+    } else {
+      const int r = tid >> 3, c = (tid & 7) >> 1, half = tid & 1;
+      a_voff = r * lda * 4 + (tid & 7) * 16;
+      aw_base = lds + r * 64 + ((c ^ f1_swz(r)) << 4) + half * 8;
+      asm volatile("" : "+v"(aw_base));
+    }
+    asm volatile("" : "+v"(a_voff), "+v"(w_voff), "+v"(fa_base), "+v"(fw_base));
+  }
+  constexpr int F1_BUF = 4 * F1_PLANE;  // 65536: one past the largest ds_* immediate
   auto load_a = [&](int t, auto) {
+    if constexpr (LEAN) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        ar[k] = buf_load16(A + (size_t)(m0 + 64 * k) * lda, a_rows[k] * lda * 4, a_voff, t * 128);
+      return;
+    }
     const int x = ltid;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -773,13 +884,26 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     }
   };
   auto store_a = [&](int u, auto) {
+    if constexpr (LEAN) {
+      LDS_AS char* const w = aw_base + u * F1_BUF;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        uint2 hi, lo;
+        split2<true>(ar[k].x, ar[k].y, hi.x, lo.x);
+        split2<true>(ar[k].z, ar[k].w, hi.y, lo.y);
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        *reinterpret_cast<LDS_AS u32x2*>(w + k * 4096) = u32x2{hi.x, hi.y};
+        *reinterpret_cast<LDS_AS u32x2*>(w + F1_PLANE + k * 4096) = u32x2{lo.x, lo.y};
+      }
+      return;
+    }
     const int x = ltid;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int r = (x >> 3) + 64 * k, c = (x & 7) >> 1, half = x & 1;
       uint2 hi, lo;
-      split2(ar[k].x, ar[k].y, hi.x, lo.x);
-      split2(ar[k].z, ar[k].w, hi.y, lo.y);
+      split2<false>(ar[k].x, ar[k].y, hi.x, lo.x);
+      split2<false>(ar[k].z, ar[k].w, hi.y, lo.y);
       const int o = r * 64 + ((c ^ f1_swz(r)) << 4) + half * 8;
       *reinterpret_cast<uint2*>(plane(u, 0) + o) = hi;
       *reinterpret_cast<uint2*>(plane(u, 1) + o) = lo;
@@ -788,6 +912,15 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
   // W: per plane 16 pieces of 16 rows (1 KiB per wave instruction), 2 per wave
   // SPLIT_IN: A hi / lo planes by DMA, 2 pieces of 16 rows per wave and plane (as W)
   auto stage_a = [&](int u, int t) {
+    if constexpr (LEAN) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          buf_glds16(a_tile, a_tile_bytes, j ? a_voff1 : a_voff, t * 128 + p * 64,
+                     plane(u, p) + (wave_u * 2 + j) * 1024);
+      return;
+    }
     const char* Ab = reinterpret_cast<const char*>(A);
     const int lane = ltid & 63, wave = ltid >> 6;
 #pragma unroll
@@ -802,6 +935,15 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     }
   };
   auto stage_w = [&](int u, int t) {
+    if constexpr (LEAN) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          buf_glds16((p ? Wl : Wh) + (size_t)n0 * ldw, F1_T * ldw * 2, w_voff, j * 16 * ldw * 2 + t * 64,
+                     plane(u, 2 + p) + (wave_u * 2 + j) * 1024);
+      return;
+    }
     const int lane = ltid & 63, wave = ltid >> 6;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -903,6 +1045,21 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
   } else {
     bf16x8 fbh[4], fbl[4], fah[8], fal[8];
     auto read_frags = [&](int u) {  // all 24 fragments of a step: 8 W, 16 A
+      if constexpr (LEAN) {
+        LDS_AS char* const fw = fw_base + u * F1_BUF;
+        LDS_AS char* const fa = fa_base + u * F1_BUF;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          fbh[j] = *reinterpret_cast<LDS_AS bf16x8*>(fw + j * 1024);
+          fbl[j] = *reinterpret_cast<LDS_AS bf16x8*>(fw + F1_PLANE + j * 1024);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          fah[i] = *reinterpret_cast<LDS_AS bf16x8*>(fa + i * 1024);
+          fal[i] = *reinterpret_cast<LDS_AS bf16x8*>(fa + F1_PLANE + i * 1024);
+        }
+        return;
+      }
       const int fr = ltid & 15, fc = (ltid >> 4) & 3, wc = (ltid >> 6) & 3, wr = ltid >> 8;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -948,6 +1105,7 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     // ahead of its MFMAs of step t-1 (the same segment 2t).
     const bool g1 = __builtin_amdgcn_readfirstlane(wr) != 0;
     auto fresh_tid = [&]() {
+      if constexpr (LEAN) return;  // nothing to recompute: the lean state is five VGPRs
       ltid = tid;
       asm volatile("" : "+v"(ltid));
     };
@@ -1008,10 +1166,10 @@ __global__ __launch_bounds__(256) void cifar_split_blocked_kernel(const float* _
       const float4 u = *reinterpret_cast<const float4*>(rowa + k * 4);
       const float4 v = *reinterpret_cast<const float4*>(rowa + k * 4 + 16);
       uint4 hi, lo;
-      split2(u.x, u.y, hi.x, lo.x);
-      split2(u.z, u.w, hi.y, lo.y);
-      split2(v.x, v.y, hi.z, lo.z);
-      split2(v.z, v.w, hi.w, lo.w);
+      split2<true>(u.x, u.y, hi.x, lo.x);
+      split2<true>(u.z, u.w, hi.y, lo.y);
+      split2<true>(v.x, v.y, hi.z, lo.z);
+      split2<true>(v.z, v.w, hi.w, lo.w);
       *reinterpret_cast<uint4*>(rowp + hoff) = hi;
       *reinterpret_cast<uint4*>(rowp + hoff + 64) = lo;
     } else {
@@ -1047,10 +1205,10 @@ __global__ __launch_bounds__(256) void cifar_split3_kernel(const float* __restri
     } else {
       const float4 u = *reinterpret_cast<const float4*>(a + (size_t)m * lda + c);
       const float4 v = *reinterpret_cast<const float4*>(a + (size_t)m * lda + c + 4);
-      split2(u.x, u.y, hi.x, lo.x);
-      split2(u.z, u.w, hi.y, lo.y);
-      split2(v.x, v.y, hi.z, lo.z);
-      split2(v.z, v.w, hi.w, lo.w);
+      split2<true>(u.x, u.y, hi.x, lo.x);
+      split2<true>(u.z, u.w, hi.y, lo.y);
+      split2<true>(v.x, v.y, hi.z, lo.z);
+      split2<true>(v.z, v.w, hi.w, lo.w);
     }
     bf16_t* r = o + (size_t)m * ldo + c;
     *reinterpret_cast<uint4*>(r) = hi;
@@ -1089,10 +1247,12 @@ __global__ __launch_bounds__(256) void cifar_head_tail_x3_kernel(const float* __
       const float4 u = *reinterpret_cast<const float4*>(ap + s * 32);
       const float4 v = *reinterpret_cast<const float4*>(ap + s * 32 + 4);
       uint4 hi, lo;
-      split2(u.x, u.y, hi.x, lo.x);
-      split2(u.z, u.w, hi.y, lo.y);
-      split2(v.x, v.y, hi.z, lo.z);
-      split2(v.z, v.w, hi.w, lo.w);
+      // split2<false>: here the compiler already pairs the conversions, and with no MFMA
+      // stream to protect its packed subtracts win (the packed form measured 37 -> 43 us)
+      split2<false>(u.x, u.y, hi.x, lo.x);
+      split2<false>(u.z, u.w, hi.y, lo.y);
+      split2<false>(v.x, v.y, hi.z, lo.z);
+      split2<false>(v.z, v.w, hi.w, lo.w);
       const bf16x8 ah = __builtin_bit_cast(bf16x8, hi), al = __builtin_bit_cast(bf16x8, lo);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wfh[s], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wfl[s], acc, 0, 0, 0);
@@ -1188,11 +1348,12 @@ extern "C" int dnn_cifar_stage0_x3(const float* x, float* out, const void* w1h, 
                    : launch_stage0_x3<false, 0>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st);
 }
 
-// fc1 k-loop schedule: 0 = lockstep, 1 = staggered wave groups (the A/B's two arms, bitwise-equal outputs)
-static int g_fc1_sched = 1;
+// fc1 k-loop schedule: 0 = lockstep, 1 = staggered wave groups, 2 = lean (staggered with the packed split and
+// loop-invariant buffer addressing); the A/B's arms, bitwise-equal outputs
+static int g_fc1_sched = 2;
 
 extern "C" int dnn_cifar_fc1_set_sched(int v) {
-  if (v < 0 || v > 1) return 1;
+  if (v < 0 || v > 2) return 1;
   g_fc1_sched = v;
   return 0;
 }
@@ -1202,7 +1363,10 @@ extern "C" int dnn_cifar_fc1_get_sched() { return g_fc1_sched; }
 template <bool SPLIT_IN>
 static int launch_fc1_x3(const float* A, int lda, const void* Wh, const void* Wl, int ldw, const float* bias, float* C,
                          int ldc, int M, int N, int K, int blocks, hipStream_t st) {
-  if (g_fc1_sched == 1)
+  if (g_fc1_sched == 2)
+    hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, true, true>), dim3(blocks), dim3(512), 0, st, A, lda,
+                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
+  else if (g_fc1_sched == 1)
     hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, true>), dim3(blocks), dim3(512), 0, st, A, lda,
                        (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
   else

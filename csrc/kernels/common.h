@@ -28,6 +28,13 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
 __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
   return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
 }
+// The same pair in one v_cvt_pk_bf16_f32 with both sources used (pack2bf's two
+// scalar conversions come out as two one-float converts plus shift / and / or).
+// Same instruction, same rounding: bitwise equal to pack2bf.
+__device__ __forceinline__ uint32_t pack2bf_pk(float lo, float hi) {
+  typedef float f32x2v __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2v{lo, hi}, bf16x2v));
+}
 
 // NaN-propagating max (llvm.maximum -> v_maximum3_f32 on gfx950).  In IEEE
 // mode fmaxf first quiets every operand the compiler cannot prove canonical

@@ -216,7 +216,9 @@ def set_stage0_conv1(packing) -> int:
     return prev
 
 
-FC1_SCHED = {"lockstep": 0, "staggered": 1}  # compiled k-loop schedules of the fused fp32 fc1 (cifar_fc1_x3)
+# compiled k-loop arms of the fused fp32 fc1 (cifar_fc1_x3); "lean" is the staggered
+# schedule with the packed bf16 split and loop-invariant buffer addressing (the default)
+FC1_SCHED = {"lockstep": 0, "staggered": 1, "lean": 2}
 
 
 def set_fc1_sched(sched) -> int:

@@ -147,6 +147,7 @@ PYBIND11_MODULE(_dnn_hip, m) {
   m.def("cifar_s0_set_conv1", [](int v) { return dnn_cifar_s0_set_conv1(v); });
   m.def("cifar_s0_get_conv1", []() { return dnn_cifar_s0_get_conv1(); });
   m.def("cifar_s0_set_wide_store", [](int on) { return dnn_cifar_s0_set_wide_store(on); });
+  m.def("cifar_s0_get_wide_store", []() { return dnn_cifar_s0_get_wide_store(); });
   m.def("cifar_s0_set_mfma", [](int v) { return dnn_cifar_s0_set_mfma(v); });
   m.def("cifar_s0_get_mfma", []() { return dnn_cifar_s0_get_mfma(); });
   m.def("cifar_split3", [](u64 a, int lda, u64 o, int ldo, int M, int K, u64 st, int blocked) {

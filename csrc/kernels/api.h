@@ -90,6 +90,7 @@ int dnn_cifar_stage0_x3(const float* x, float* out, const void* w1h, const void*
 int dnn_cifar_s0_set_conv1(int v);
 int dnn_cifar_s0_get_conv1();
 int dnn_cifar_s0_set_wide_store(int on);
+int dnn_cifar_s0_get_wide_store();
 int dnn_cifar_s0_set_mfma(int v);
 int dnn_cifar_s0_get_mfma();
 int dnn_cifar_split3(const float* a, int lda, void* o, int ldo, int M, int K, hipStream_t st, int blocked = 0);

@@ -12,62 +12,13 @@
 //   persistent loop (one 32-channel N-tile per wave = 72 VGPRs).
 //
 // Stage 1 tail (reference ModelPart1_2Node, cifar_model_parts.py:53-58, plus the
-// host-side argmax of node.py:61/190, done per row here): after fc1+bias+ReLU
-// (gemm_bf16 with ACT_RELU), fc2(512->10)+bias+softmax+argmax on MFMA, 16 rows
-// per wave-iteration.
+// host-side argmax of node.py:61/190, done per row): after fc1+bias+ReLU
+// (gemm_bf16 with ACT_RELU), fc2(512->10)+bias+softmax+argmax is
+// cifar_head_tail_kernel in cifar_x3.hip: this file is built with -ffast-math,
+// which turns the softmax's exp into v_exp_f32(log2e * x).
 #include "common.h"
 
 namespace dnn {
-
-
-// fc2 (512->10) + bias + softmax + argmax. hid: (B,512) bf16 (fc1+ReLU output).
-// One wave handles 16 rows per iteration with mfma_f32_16x16x32_bf16:
-// A = hid rows (lane: row l&15, k 8*(l>>4)+j), B = W2 padded to 16 classes held
-// in VGPRs. Softmax across each 16-lane row group with xor-shuffles.
-__global__ __launch_bounds__(256) void cifar_head_tail_kernel(const bf16_t* __restrict__ hid, const bf16_t* __restrict__ w2p,
-                                                              const float* __restrict__ b2, float* __restrict__ probs,
-                                                              int* __restrict__ pred, int B) {
-  const int lane = threadIdx.x & 63;
-  const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int nw = (gridDim.x * blockDim.x) >> 6;
-  const int col = lane & 15, kq = (lane >> 4) * 8;
-  bf16x8 wf[16];
-#pragma unroll
-  for (int s = 0; s < 16; ++s) wf[s] = *reinterpret_cast<const bf16x8*>(w2p + col * 512 + s * 32 + kq);
-  const float bias = col < 10 ? b2[col] : 0.f;
-  for (int r0 = gw * 16; r0 < B; r0 += nw * 16) {
-    const int row = r0 + (lane & 15);
-    const int rc = row < B ? row : B - 1;
-    const bf16_t* ap = hid + (size_t)rc * 512 + kq;
-    bf16x8 a[16];
-#pragma unroll
-    for (int s = 0; s < 16; ++s) a[s] = *reinterpret_cast<const bf16x8*>(ap + s * 32);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s], wf[s], acc, 0, 0, 0);
-    // acc[r] = logit(row = r0 + (lane>>4)*4 + r, class = col)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float z = col < 10 ? acc[r] + bias : -INFINITY;
-      float mx = z;
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-      const float e = col < 10 ? __expf(z - mx) : 0.f;
-      float sum = e;
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
-      // argmax: smallest class index attaining the max (numpy semantics)
-      int cand = (z == mx) ? col : 16;
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-      const int m = r0 + (lane >> 4) * 4 + r;
-      if (m < B) {
-        if (col < 10) probs[(size_t)m * 10 + col] = e / sum;
-        if (col == 0) pred[m] = cand;
-      }
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------
 // Stage-0 LDS layouts (shared by the v4 kernel below):
@@ -399,16 +350,4 @@ extern "C" int dnn_cifar_set_v4_pt(int pt) {
   if (pt < 0 || pt > 32 || pt % 4 != 0) return -1;
   g_v4_pt = pt;
   return 0;
-}
-
-
-extern "C" int dnn_cifar_head_tail(const void* hid, const void* w2p, const float* b2, float* probs, int* pred, int B,
-                                   hipStream_t st) {
-  if (B <= 0) return 0;
-  int waves = (B + 15) / 16;
-  int blocks = (waves + 3) / 4;
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(cifar_head_tail_kernel, dim3(blocks), dim3(256), 0, st, (const bf16_t*)hid, (const bf16_t*)w2p,
-                     b2, probs, pred, B);
-  return (int)hipGetLastError();
 }

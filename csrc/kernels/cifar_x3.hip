@@ -70,6 +70,8 @@
 //    W' = [W_hi | W_lo | W_hi]) when the 256^2 tiles cannot fill the chip.
 //  * cifar_head_tail_x3_kernel: fc2 (512->10) + bias + softmax + per-row argmax
 //    on fp32 hidden rows, 3-term split on mfma_f32_16x16x32_bf16.
+//  * cifar_head_tail_kernel: the same on bf16 hidden rows and bf16 fc2 weights (the
+//    bf16 precision's head tail; here for this file's IEEE exp and division).
 #include <type_traits>
 
 #include "gemm_epilogue.h"
@@ -1281,6 +1283,61 @@ __global__ __launch_bounds__(256) void cifar_head_tail_x3_kernel(const float* __
   }
 }
 
+// The bf16 precision's head tail: fc2 (512->10) + bias + softmax + argmax. hid: (B,512) bf16
+// (fc1+ReLU output).  One wave handles 16 rows per iteration with mfma_f32_16x16x32_bf16:
+// A = hid rows (lane: row l&15, k 8*(l>>4)+j), B = W2 padded to 16 classes held
+// in VGPRs. Softmax across each 16-lane row group with xor-shuffles.
+// It lives in this file, not in cifar_fused.hip, for the IEEE expf and division of this file's
+// build: under cifar_fused.hip's -ffast-math, expf (and __expf under any flags) is
+// v_exp_f32(log2e * x), whose rounded product is a relative error of the probability that grows
+// with the gap to the max (3.5e-6 measured at a gap of 72), and __expf also flushes probabilities
+// below 2^-126 to 0.  The IEEE forms cost 0.4 us of 18 at B = 65536.  The probabilities are fp32
+// outputs in both precisions, held to one bound (tests/test_cifar_head_tail_gpu.py).
+__global__ __launch_bounds__(256) void cifar_head_tail_kernel(const bf16_t* __restrict__ hid, const bf16_t* __restrict__ w2p,
+                                                              const float* __restrict__ b2, float* __restrict__ probs,
+                                                              int* __restrict__ pred, int B) {
+  const int lane = threadIdx.x & 63;
+  const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nw = (gridDim.x * blockDim.x) >> 6;
+  const int col = lane & 15, kq = (lane >> 4) * 8;
+  bf16x8 wf[16];
+#pragma unroll
+  for (int s = 0; s < 16; ++s) wf[s] = *reinterpret_cast<const bf16x8*>(w2p + col * 512 + s * 32 + kq);
+  const float bias = col < 10 ? b2[col] : 0.f;
+  for (int r0 = gw * 16; r0 < B; r0 += nw * 16) {
+    const int row = r0 + (lane & 15);
+    const int rc = row < B ? row : B - 1;
+    const bf16_t* ap = hid + (size_t)rc * 512 + kq;
+    bf16x8 a[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) a[s] = *reinterpret_cast<const bf16x8*>(ap + s * 32);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s], wf[s], acc, 0, 0, 0);
+    // acc[r] = logit(row = r0 + (lane>>4)*4 + r, class = col)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float z = col < 10 ? acc[r] + bias : -INFINITY;
+      float mx = z;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      const float e = col < 10 ? expf(z - mx) : 0.f;
+      float sum = e;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
+      // argmax: smallest class index attaining the max (numpy semantics)
+      int cand = (z == mx) ? col : 16;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+      const int m = r0 + (lane >> 4) * 4 + r;
+      if (m < B) {
+        if (col < 10) probs[(size_t)m * 10 + col] = e / sum;
+        if (col == 0) pred[m] = cand;
+      }
+    }
+  }
+}
+
 }  // namespace dnn
 
 using namespace dnn;
@@ -1303,6 +1360,8 @@ extern "C" int dnn_cifar_s0_set_wide_store(int on) {
   g_s0_wide_store = on ? 1 : 0;
   return 0;
 }
+
+extern "C" int dnn_cifar_s0_get_wide_store() { return g_s0_wide_store; }
 
 // conv1 K packing: 1 = K = 32 on channel-packed planes (default; every interleaved round faster than
 // K = 48, profiles/cifar_conv1_k32_ab.jsonl), 0 = K = 48 on HWC4 planes (the A/B's other arm)
@@ -1412,5 +1471,16 @@ extern "C" int dnn_cifar_head_tail_x3(const float* hid, const void* w2h, const v
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(cifar_head_tail_x3_kernel, dim3(blocks), dim3(256), 0, st, hid, (const bf16_t*)w2h,
                      (const bf16_t*)w2l, b2, probs, pred, B);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dnn_cifar_head_tail(const void* hid, const void* w2p, const float* b2, float* probs, int* pred, int B,
+                                   hipStream_t st) {
+  if (B <= 0) return 0;
+  int waves = (B + 15) / 16;
+  int blocks = (waves + 3) / 4;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(cifar_head_tail_kernel, dim3(blocks), dim3(256), 0, st, (const bf16_t*)hid, (const bf16_t*)w2p,
+                     b2, probs, pred, B);
   return (int)hipGetLastError();
 }

@@ -204,6 +204,15 @@ def set_stage0_mfma(shape) -> int:
     return prev
 
 
+def set_stage0_wide_store(on) -> int:
+    """Boundary stores of the 32x32x16 conv2 consumer: 16-byte (1, the default) or
+    8-byte (0); the 16x16x32 consumer ignores it.  Returns the previous setting so
+    callers can restore it."""
+    prev = lib().cifar_s0_get_wide_store()
+    check(lib().cifar_s0_set_wide_store(int(bool(on))), "cifar_s0_set_wide_store")
+    return prev
+
+
 STAGE0_CONV1 = {"k48": 0, "k32": 1}  # compiled conv1 producer paths (fp32); 1 is the default
 
 

@@ -8,8 +8,10 @@ of the 27 taps alone and the halo.
 Shapes and bounds are those of test_cifar_stage0_mfma_gpu.py: one image
 (prologue and drain only), two images in one workgroup (both double-buffer
 parities), 4 + 3 images in two workgroups, 257 images on the default grid;
-2e-5 * max(1, max|mid|) on the boundary, 1e-5 on the probabilities.  The two
-conv1 arms are not compared with each other: they sum K in different orders.
+2e-5 * max(1, max|mid|) on the boundary, 1e-5 on the probabilities.  On these
+inputs the two conv1 arms are not compared with each other: they sum K in
+different orders.  tests/test_cifar_stage0_exact_gpu.py compares them bitwise, on
+inputs for which every order gives the same bits.
 """
 import functools
 

@@ -9,7 +9,9 @@ go wrong: one image (prologue and drain only), two images in one workgroup
 parity wrap), and 257 images on the default grid (one workgroup with two images
 beside 255 with one).  The bounds are those of test_kernels_gpu.py's
 test_cifar_fp32_stage0_and_head and test_cifar_split_boundary_bit_identical.
-The arms are not compared with each other: the shapes sum K in different orders.
+On these inputs the arms are not compared with each other: the shapes sum K in
+different orders.  tests/test_cifar_stage0_exact_gpu.py compares them bitwise, on
+inputs for which every order gives the same bits.
 """
 import functools
 

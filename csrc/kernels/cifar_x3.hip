@@ -59,12 +59,12 @@
 //    tiles, 8 waves of 128x64, per k32 step 3 x 32 mfma_f32_16x16x32_bf16 per
 //    wave (A_hi W_hi + A_hi W_lo + A_lo W_hi) on 24 conflict-free ds_read_b128.
 //    Waves 0-3 and 4-7 run half a k-step apart, so each SIMD pairs a wave
-//    issuing MFMAs with one reading, splitting and restaging ("STAG" below).
-//    The default arm is "LEAN": that schedule with the packed split
+//    issuing MFMAs with one reading, splitting and restaging (the schedule above
+//    the kernel).  The default arm is "LEAN": that schedule with the packed split
 //    (split2<true>) and all global addressing through buffer descriptors, 51
-//    non-MFMA vector instructions per k-step instead of 207; the staggered and
-//    the lockstep loops stay compiled as the A/B's other arms, on the code they
-//    had (dnn_cifar_fc1_set_sched: 0 lockstep, 1 staggered, 2 lean).
+//    non-MFMA vector instructions per k-step instead of 207; the same schedule
+//    with scalar conversions and per-segment addressing stays compiled as the
+//    A/B's other arm (dnn_cifar_fc1_set_sched: 1 staggered, 2 lean).
 //  * cifar_split3_kernel: fp32 (B,K) -> bf16 (B,3K) = [hi | hi | lo], the A
 //    operand of the small-batch fc1 (one skinny bf16 GEMM over K' = 3K against
 //    W' = [W_hi | W_lo | W_hi]) when the 256^2 tiles cannot fill the chip.
@@ -83,8 +83,8 @@ namespace x3 {
 // PK: both conversions as one v_cvt_pk_bf16_f32 per pair (6 VALU per pair
 // instead of ~11.5, bitwise the same values); the empty asm keeps the two
 // subtracts scalar (SLP would pack them into v_pk_add_f32, which costs more
-// than it saves beside MFMAs).  PK = false is the form the lockstep and
-// staggered fc1 arms and the head kernel keep: their code is unchanged.
+// than it saves beside MFMAs).  PK = false is the form the
+// staggered fc1 arm and the head kernel keep: their code is unchanged.
 template <bool PK>
 __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
   if constexpr (PK) {
@@ -717,9 +717,8 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
 // four ds_read_b128 lane groups ({0-3,12-15,20-27}, ...) of a fragment read
 // (lane: row l & 15, chunk l >> 4) then hit 16 distinct slots, and the A
 // writes (8 contiguous lanes = 2 rows x 4 chunks) 8 distinct ds_write slots.
-// Lockstep schedule: one barrier per k32 step, the step's next-tile loads are
-// issued before its MFMAs and land in the other buffer.  Staggered schedule
-// (the default): see STAG at the kernel.
+// The k loop's schedule (two wave groups half a k-step apart) is described at
+// the kernel.
 // ---------------------------------------------------------------------------
 constexpr int F1_T = 256, F1_K = 32, F1_PLANE = 256 * 64;
 
@@ -747,8 +746,8 @@ __device__ __forceinline__ void f1_tile_coords(int logical, int ntm, int ntn, in
 // 0.51 ms, without any load 0.45 ms (1.8 PF/s), with both 0.80 ms.  On the
 // staggered schedule (profiles/cifar_fc1_sched_ab.jsonl): s_setprio 1 around
 // the MFMA segment and static s_setprio 1 for waves 4-7 both lost 0.4-0.5 %;
-// the bias in registers with a branch-free store path for full tiles was a
-// tie on lockstep and -0.75 % with overlapping rounds on staggered: dropped.
+// the bias in registers with a branch-free store path for full tiles was
+// -0.75 % with overlapping rounds: dropped.
 //
 // SPLIT_IN: A arrives pre-split in the blocked boundary encoding (see
 // cifar_split_blocked_kernel: per row and 32-k block, 32 bf16 hi then 32 bf16
@@ -756,9 +755,11 @@ __device__ __forceinline__ void f1_tile_coords(int logical, int ntm, int ntn, in
 // form in registers), so A is staged by DMA exactly like W: no VGPR round
 // trip, no split ALU, no vmcnt stall on A inside the k loop.
 //
-// STAG: the staggered schedule.  Lockstep (STAG = false), all eight waves read
-// their fragments, multiply and restage at the same time, so a SIMD's matrix
-// pipe idles while both of its waves read or split.  Staggered, group 0 (waves
+// Schedule.  With all eight waves reading their fragments, multiplying and
+// restaging at the same time (one barrier per k-step), a SIMD's matrix pipe
+// idles while both of its waves read or split: every interleaved round slower,
+// with bitwise the same outputs (profiles/cifar_fc1_sched_ab.jsonl,
+// profiles/cifar_fc1_sched_after.md).  So group 0 (waves
 // 0-3, rows 0-127 of the tile) and group 1 (waves 4-7) run half a k-step apart:
 // a k-step is two segments between s_barriers, and in each segment one wave of
 // every SIMD issues its 96 MFMAs from 24 fragments already in registers while
@@ -776,10 +777,10 @@ __device__ __forceinline__ void f1_tile_coords(int logical, int ntm, int ntn, in
 // and after the step's DMAs in program order, so vmcnt(4) retires the DMAs and
 // leaves the A loads in flight.  Every wave passes 1 + 2 nk barriers for any
 // nk >= 1: group 0 ends with the barrier after its last MFMAs and goes to its
-// epilogue while group 1 runs its last MFMA segment.  Each accumulator sees the
-// same MFMAs in the same order as lockstep: the outputs are bitwise equal.
+// epilogue while group 1 runs its last MFMA segment.  Each accumulator sees its
+// MFMAs in k order, W_hi A_hi, W_lo A_hi, W_hi A_lo per k-step, in both groups.
 //
-// LEAN (with STAG): the same segments, barriers, counted vmcnt and MFMA order,
+// LEAN: the same segments, barriers, counted vmcnt and MFMA order,
 // with what a load segment issues next to its partner's MFMAs cut to the split
 // itself.  The staggered arm rebuilds every row pointer and LDS offset per
 // segment (64-bit per-lane arithmetic, ~85 VALU per k-step) because it has no
@@ -798,9 +799,9 @@ __device__ __forceinline__ void f1_tile_coords(int logical, int ntm, int ntn, in
 // lane offset), so such a row is dropped by the range check, reads as zero and
 // is never stored.  split2<true> converts each pair with one
 // v_cvt_pk_bf16_f32: the same instruction and rounding on the same values, so
-// the outputs are bitwise those of the other arms.  Measured in
+// the outputs are bitwise those of the other arm.  Measured in
 // profiles/cifar_lean_after.md: fc1 0.646 -> 0.572 ms interleaved, every round.
-template <bool SPLIT_IN, bool STAG = false, bool LEAN = false>
+template <bool SPLIT_IN, bool LEAN>
 __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __restrict__ A, int lda,
                                                               const bf16_t* __restrict__ Wh,
                                                               const bf16_t* __restrict__ Wl, int ldw,
@@ -831,7 +832,6 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
   float4 ar[4];
   // LEAN addressing (see above the kernel): descriptors from block-uniform
   // values, one 32-bit lane offset per stream, one LDS base per access kind.
-  static_assert(!LEAN || STAG, "the lean arm is the staggered schedule");
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   // fp32 A, piece k (rows m0 + 64 k ..+63): the records end with row M - 1, so
   // a row past M is dropped by the range check (reads as 0, is never stored)
@@ -975,50 +975,15 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     stage_w(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     store_a(0, I0{});
-    if constexpr (STAG) {
-      if (nk > 1) load_a(1, I0{});  // both groups split A(1) in their first load segment
-    }
+    if (nk > 1) load_a(1, I0{});  // both groups split A(1) in their first load segment
   }
-  if constexpr (STAG) {  // raw barrier: A(1) stays in flight across it
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  } else {
-    __syncthreads();
-  }
+  // raw barrier: A(1) stays in flight across it
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
 
-  const int fr = lane & 15, fc = lane >> 4;
-  auto compute = [&](int u) {
-    const char* ah_p = plane(u, 0);
-    const char* al_p = plane(u, 1);
-    const char* bh_p = plane(u, 2);
-    const char* bl_p = plane(u, 3);
-    bf16x8 bh[4], bl[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      bh[j] = f1_frag(bh_p, wc * 64 + j * 16 + fr, fc);
-      bl[j] = f1_frag(bl_p, wc * 64 + j * 16 + fr, fc);
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      bf16x8 ah[4], al[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ah[i] = f1_frag(ah_p, wr * 128 + (h * 4 + i) * 16 + fr, fc);
-        al[i] = f1_frag(al_p, wr * 128 + (h * 4 + i) * 16 + fr, fc);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          f32x4& a = acc[h * 4 + i][j];
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[i], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah[i], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al[i], a, 0, 0, 0);
-        }
-    }
-  };
+  const int fr = lane & 15, fc = lane >> 4;  // epilogue lane map
   // raw barrier (lgkmcnt for this step's LDS writes; the DMAs were waited
   // above): 6 % faster than __syncthreads here
   auto barrier = [&]() {
@@ -1027,117 +992,98 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
-  if constexpr (!STAG) {
-    for (int t = 0; t < nk; ++t) {
-      const int u = t & 1;
-      if (t + 1 < nk) {
-        if constexpr (SPLIT_IN)
-          stage_a(u ^ 1, t + 1);
-        else
-          load_a(t + 1, I0{});
-        stage_w(u ^ 1, t + 1);
-      }
-      compute(u);
-      if (t + 1 < nk) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (!SPLIT_IN) store_a(u ^ 1, I0{});
-      }
-      barrier();
-    }
-  } else {
-    bf16x8 fbh[4], fbl[4], fah[8], fal[8];
-    auto read_frags = [&](int u) {  // all 24 fragments of a step: 8 W, 16 A
-      if constexpr (LEAN) {
-        LDS_AS char* const fw = fw_base + u * F1_BUF;
-        LDS_AS char* const fa = fa_base + u * F1_BUF;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          fbh[j] = *reinterpret_cast<LDS_AS bf16x8*>(fw + j * 1024);
-          fbl[j] = *reinterpret_cast<LDS_AS bf16x8*>(fw + F1_PLANE + j * 1024);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          fah[i] = *reinterpret_cast<LDS_AS bf16x8*>(fa + i * 1024);
-          fal[i] = *reinterpret_cast<LDS_AS bf16x8*>(fa + F1_PLANE + i * 1024);
-        }
-        return;
-      }
-      const int fr = ltid & 15, fc = (ltid >> 4) & 3, wc = (ltid >> 6) & 3, wr = ltid >> 8;
+  bf16x8 fbh[4], fbl[4], fah[8], fal[8];
+  auto read_frags = [&](int u) {  // all 24 fragments of a step: 8 W, 16 A
+    if constexpr (LEAN) {
+      LDS_AS char* const fw = fw_base + u * F1_BUF;
+      LDS_AS char* const fa = fa_base + u * F1_BUF;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        fbh[j] = f1_frag(plane(u, 2), wc * 64 + j * 16 + fr, fc);
-        fbl[j] = f1_frag(plane(u, 3), wc * 64 + j * 16 + fr, fc);
+        fbh[j] = *reinterpret_cast<LDS_AS bf16x8*>(fw + j * 1024);
+        fbl[j] = *reinterpret_cast<LDS_AS bf16x8*>(fw + F1_PLANE + j * 1024);
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        fah[i] = f1_frag(plane(u, 0), wr * 128 + i * 16 + fr, fc);
-        fal[i] = f1_frag(plane(u, 1), wr * 128 + i * 16 + fr, fc);
+        fah[i] = *reinterpret_cast<LDS_AS bf16x8*>(fa + i * 1024);
+        fal[i] = *reinterpret_cast<LDS_AS bf16x8*>(fa + F1_PLANE + i * 1024);
       }
-    };
-    // per accumulator W_hi A_hi, W_lo A_hi, W_hi A_lo as in compute(); term-major
-    // inside a row block so that consecutive MFMAs never share an accumulator
-    auto mfma_seg = [&]() {
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int term = 0; term < 3; ++term)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 1 ? fbl[j] : fbh[j], term == 2 ? fal[i] : fah[i],
-                                                                acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    // retire this wave's DMAs of the next step; the 4 A loads issued after them stay in flight
-    auto retire_dma = [&](bool a_in_flight) {
-      if (a_in_flight)
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    auto stage_next = [&](int u, int t) {
-      if constexpr (SPLIT_IN) stage_a(u, t);
-      stage_w(u, t);
-    };
-    // One program for both groups, group 1 one barrier behind: it passes an extra
-    // barrier ahead of the loop (segment 0, where it only issues the DMAs of step
-    // 1) and skips the one after its last MFMA segment, which group 0 passes on
-    // its way to the epilogue.  What differs is where a group's DMAs sit: group 0
-    // issues those of step t+1 in its load segment of step t (segment 2t), group 1
-    // ahead of its MFMAs of step t-1 (the same segment 2t).
-    const bool g1 = __builtin_amdgcn_readfirstlane(wr) != 0;
-    auto fresh_tid = [&]() {
-      if constexpr (LEAN) return;  // nothing to recompute: the lean state is five VGPRs
-      ltid = tid;
-      asm volatile("" : "+v"(ltid));
-    };
-    if (g1) {
-      if (nk > 1) stage_next(1, 1);
-      barrier();
+      return;
     }
-    for (int t = 0; t < nk; ++t) {
-      const int u = t & 1;
-      // load segment: group 0 segment 2t, group 1 segment 2t + 1
+    const int fr = ltid & 15, fc = (ltid >> 4) & 3, wc = (ltid >> 6) & 3, wr = ltid >> 8;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      fbh[j] = f1_frag(plane(u, 2), wc * 64 + j * 16 + fr, fc);
+      fbl[j] = f1_frag(plane(u, 3), wc * 64 + j * 16 + fr, fc);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      fah[i] = f1_frag(plane(u, 0), wr * 128 + i * 16 + fr, fc);
+      fal[i] = f1_frag(plane(u, 1), wr * 128 + i * 16 + fr, fc);
+    }
+  };
+  // per accumulator W_hi A_hi, W_lo A_hi, W_hi A_lo; term-major
+  // inside a row block so that consecutive MFMAs never share an accumulator
+  auto mfma_seg = [&]() {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int term = 0; term < 3; ++term)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 1 ? fbl[j] : fbh[j], term == 2 ? fal[i] : fah[i],
+                                                              acc[i][j], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // retire this wave's DMAs of the next step; the 4 A loads issued after them stay in flight
+  auto retire_dma = [&](bool a_in_flight) {
+    if (a_in_flight)
+      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  };
+  auto stage_next = [&](int u, int t) {
+    if constexpr (SPLIT_IN) stage_a(u, t);
+    stage_w(u, t);
+  };
+  // One program for both groups, group 1 one barrier behind: it passes an extra
+  // barrier ahead of the loop (segment 0, where it only issues the DMAs of step
+  // 1) and skips the one after its last MFMA segment, which group 0 passes on
+  // its way to the epilogue.  What differs is where a group's DMAs sit: group 0
+  // issues those of step t+1 in its load segment of step t (segment 2t), group 1
+  // ahead of its MFMAs of step t-1 (the same segment 2t).
+  const bool g1 = __builtin_amdgcn_readfirstlane(wr) != 0;
+  auto fresh_tid = [&]() {
+    if constexpr (LEAN) return;  // nothing to recompute: the lean state is five VGPRs
+    ltid = tid;
+    asm volatile("" : "+v"(ltid));
+  };
+  if (g1) {
+    if (nk > 1) stage_next(1, 1);
+    barrier();
+  }
+  for (int t = 0; t < nk; ++t) {
+    const int u = t & 1;
+    // load segment: group 0 segment 2t, group 1 segment 2t + 1
+    fresh_tid();
+    read_frags(u);
+    if (t + 1 < nk) {
+      if constexpr (!SPLIT_IN) store_a(u ^ 1, I0{});
+      if (!g1) stage_next(u ^ 1, t + 1);
+      if constexpr (!SPLIT_IN) {
+        if (t + 2 < nk) load_a(t + 2, I0{});
+      }
+      if (g1) retire_dma(!SPLIT_IN && t + 2 < nk);
+    }
+    barrier();
+    // MFMA segment: group 0 segment 2t + 1, group 1 segment 2t + 2
+    if (g1 && t + 2 < nk) {
       fresh_tid();
-      read_frags(u);
-      if (t + 1 < nk) {
-        if constexpr (!SPLIT_IN) store_a(u ^ 1, I0{});
-        if (!g1) stage_next(u ^ 1, t + 1);
-        if constexpr (!SPLIT_IN) {
-          if (t + 2 < nk) load_a(t + 2, I0{});
-        }
-        if (g1) retire_dma(!SPLIT_IN && t + 2 < nk);
-      }
-      barrier();
-      // MFMA segment: group 0 segment 2t + 1, group 1 segment 2t + 2
-      if (g1 && t + 2 < nk) {
-        fresh_tid();
-        stage_next(u, t + 2);
-      }
-      mfma_seg();
-      if (!g1 && t + 1 < nk) retire_dma(!SPLIT_IN && t + 2 < nk);
-      if (!g1 || t + 1 < nk) barrier();
+      stage_next(u, t + 2);
     }
+    mfma_seg();
+    if (!g1 && t + 1 < nk) retire_dma(!SPLIT_IN && t + 2 < nk);
+    if (!g1 || t + 1 < nk) barrier();
   }
 
   // epilogue (transposed accumulators): row m0 + wr*128 + i*16 + (lane & 15), cols n..n+3
@@ -1407,12 +1353,12 @@ extern "C" int dnn_cifar_stage0_x3(const float* x, float* out, const void* w1h, 
                    : launch_stage0_x3<false, 0>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st);
 }
 
-// fc1 k-loop schedule: 0 = lockstep, 1 = staggered wave groups, 2 = lean (staggered with the packed split and
+// fc1 k-loop arm: 1 = staggered wave groups, 2 = lean (the same schedule with the packed split and
 // loop-invariant buffer addressing); the A/B's arms, bitwise-equal outputs
 static int g_fc1_sched = 2;
 
 extern "C" int dnn_cifar_fc1_set_sched(int v) {
-  if (v < 0 || v > 2) return 1;
+  if (v < 1 || v > 2) return 1;
   g_fc1_sched = v;
   return 0;
 }
@@ -1423,9 +1369,6 @@ template <bool SPLIT_IN>
 static int launch_fc1_x3(const float* A, int lda, const void* Wh, const void* Wl, int ldw, const float* bias, float* C,
                          int ldc, int M, int N, int K, int blocks, hipStream_t st) {
   if (g_fc1_sched == 2)
-    hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, true, true>), dim3(blocks), dim3(512), 0, st, A, lda,
-                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
-  else if (g_fc1_sched == 1)
     hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, true>), dim3(blocks), dim3(512), 0, st, A, lda,
                        (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
   else

@@ -225,9 +225,9 @@ def set_stage0_conv1(packing) -> int:
     return prev
 
 
-# compiled k-loop arms of the fused fp32 fc1 (cifar_fc1_x3); "lean" is the staggered
-# schedule with the packed bf16 split and loop-invariant buffer addressing (the default)
-FC1_SCHED = {"lockstep": 0, "staggered": 1, "lean": 2}
+# compiled k-loop arms of the fused fp32 fc1 (cifar_fc1_x3), both on the staggered schedule; "lean"
+# adds the packed bf16 split and loop-invariant buffer addressing (the default)
+FC1_SCHED = {"staggered": 1, "lean": 2}
 
 
 def set_fc1_sched(sched) -> int:

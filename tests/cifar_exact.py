@@ -1,10 +1,11 @@
-"""Exact-arithmetic fixtures for the fp32 CIFAR stage 0 (helper module, no tests).
+"""Exact-arithmetic fixtures for the fp32 CIFAR kernels: stage 0 first, the head tail and the
+fused fc1 further down (helper module, no tests).
 
 The fp32 kernels compute every layer as ``a_hi*w_hi + a_hi*w_lo + a_lo*w_hi`` on
 bf16 MFMAs with fp32 accumulation.  With inputs and weights on power-of-two
 grids, every product and every partial sum is exactly representable in fp32, so
 the result is the same in every summation order and the fp64 torch stage, cast
-to fp32, is the bit-exact expected output of every arm.  Let ``u`` be the
+to fp32, is the bit-exact expected output.  Let ``u`` be the
 product of the two operands' grid steps of a layer; the layer is exact if
 
   (i)   each operand equals its ``split_bf16`` ``hi + lo`` exactly,
@@ -338,3 +339,81 @@ def emulate_head_logits_fp32(fx: HeadFixture, order_seed=None) -> torch.Tensor:
                 acc = acc + hh[:, k:k + 1] * wl[None, :, k]
                 acc = acc + hl[:, k:k + 1] * wh[None, :, k]
     return acc + fx.sd["fc2.bias"]
+
+
+# ---------------------------------------------------------------------------
+# Fused fc1 (relu(A . W^T + b), K = 4096): exact outputs.  K = 4096 costs 12
+# bits, so the narrow operand is five values wide; the wide one carries 10 bits
+# and so a nonzero lo half.  Every product and partial sum is a whole number of
+# units below 2^24, so relu(A . W^T + b) in fp64, cast to fp32, is the expected
+# output bit for bit in any summation order.
+#
+#   fixture   A                W               b               u       exercises
+#   a_wide    511 * 2^-7       2 * 2^-1        32768 * 2^-8    2^-8    a_lo * w_hi
+#   w_wide    2 * 2^-1         511 * 2^-9      32768 * 2^-10   2^-10   a_hi * w_lo
+#
+# Worst case by construction: 4096*511*2 + 32768 units, below 2^23.  The bias is
+# of the size of the sums (standard deviation about 27000 units at K = 4096), so
+# that the sign under the ReLU depends on the product, not on the bias alone.
+# Every smaller shape is a prefix: rows [:M] of A, rows [:N] of W and of b,
+# columns [:K] of both.
+# ---------------------------------------------------------------------------
+FC1_NAMES = ("a_wide", "w_wide")
+FC1_M_MAX, FC1_N, FC1_K = 300, 512, 4096
+_FC1 = {  # name: (A max int, A step, W max int, W step, bias max int)
+    "a_wide": (511, 2.0**-7, 2, 2.0**-1, 32768),
+    "w_wide": (2, 2.0**-1, 511, 2.0**-9, 32768),
+}
+
+
+@dataclass(frozen=True)
+class Fc1Fixture:
+    name: str
+    a: torch.Tensor     # (M,K) fp32
+    w: torch.Tensor     # (N,K) fp32
+    b: torch.Tensor     # (N,) fp32, on the product grid
+    u: float            # the outputs' grid step
+    bound_units: float  # worst case of sum(|a||w|) + |b| in units, by construction
+
+
+@functools.lru_cache(maxsize=None)
+def _build_fc1(name: str, seed: int) -> Fc1Fixture:
+    am, astep, wm, wstep, bm = _FC1[name]
+    g = torch.Generator().manual_seed(1000 * seed + 200 + FC1_NAMES.index(name))
+    a = _ints(g, am, (FC1_M_MAX, FC1_K)) * astep
+    w = _ints(g, wm, (FC1_N, FC1_K)) * wstep
+    u = astep * wstep
+    b = _ints(g, bm, (FC1_N,)) * u
+    for t in (a, w, b):
+        assert torch.equal(t.float().double(), t)  # the grids are exact in fp32
+    return Fc1Fixture(name, a.float(), w.float(), b.float(), u, float(FC1_K * am * wm + bm))
+
+
+def fc1_fixture(name: str, M: int = FC1_M_MAX, N: int = FC1_N, K: int = FC1_K, seed: int = SEED) -> Fc1Fixture:
+    """Fixture ``name`` cut to (M, N, K): the first rows and columns of the one generated."""
+    if not (1 <= M <= FC1_M_MAX and 1 <= N <= FC1_N and 1 <= K <= FC1_K):
+        raise ValueError(f"shape must be within {(FC1_M_MAX, FC1_N, FC1_K)}")
+    fx = _build_fc1(name, seed)
+    return Fc1Fixture(fx.name, fx.a[:M, :K], fx.w[:N, :K], fx.b[:N], fx.u, fx.bound_units)
+
+
+def fc1_reference64(fx: Fc1Fixture) -> torch.Tensor:
+    """relu(A . W^T + b) in fp64: (M,N), exact.  ``+ 0.0`` makes every zero a positive zero."""
+    return torch.relu(fx.a.double() @ fx.w.double().t() + fx.b.double()) + 0.0
+
+
+def emulate_fc1_fp32(fx: Fc1Fixture, order_seed=None) -> torch.Tensor:
+    """fc1 as the fused kernel accumulates it, in fp32 throughout: per k the three bf16-term
+    products, then bias and ReLU.  ``order_seed`` None: k in its natural order; else a random order."""
+    K = fx.a.shape[1]
+    order = (torch.arange(K) if order_seed is None
+             else torch.randperm(K, generator=torch.Generator().manual_seed(order_seed)))
+    ah, al = split_bf16(fx.a)
+    wh, wl = split_bf16(fx.w)
+    acc = torch.zeros(fx.a.shape[0], fx.w.shape[0], dtype=torch.float32)
+    with _one_thread():
+        for k in order.tolist():
+            acc = acc + ah[:, k:k + 1] * wh[None, :, k]
+            acc = acc + ah[:, k:k + 1] * wl[None, :, k]
+            acc = acc + al[:, k:k + 1] * wh[None, :, k]
+    return torch.relu(acc + fx.b) + 0.0

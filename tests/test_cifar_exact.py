@@ -15,6 +15,9 @@ if they hold.  Seed 0 at B = 3 gives (units of the layer's grid step)
 
 all below 2^22 = 4194304, conv1's below 2^16; the 257 images the GPU tests use
 stay below 60000 and 850000 (asserted there on the data, once per fixture).
+
+The head-tail and fused-fc1 fixtures of the same module follow, held to the
+same preconditions.
 """
 import pytest
 import torch
@@ -154,3 +157,56 @@ def test_head_logits_spread_ties_and_underflow(hfx):
     assert bool((p32[::8] == 0).any(dim=1).all())
     for B in (1, 15, 16, 17):
         assert torch.equal(ce.head_fixture(hfx.name, B).hid, hfx.hid[:B])
+
+
+# --- fused fc1 fixtures -----------------------------------------------------------------------
+
+@pytest.fixture(params=ce.FC1_NAMES)
+def ffx(request):
+    return ce.fc1_fixture(request.param)
+
+
+def test_fc1_operands_and_headroom(ffx):
+    """(i)-(iii) for fc1: operands equal their split, exactly one of them is bf16-exact and the other
+    has a well-filled lo half, and sum(|a||w|) + |b| is below 2^24 units by construction and on the data."""
+    for what, t in (("a", ffx.a), ("w", ffx.w)):
+        hi, lo = ce.split_bf16(t)
+        assert torch.equal(hi.double() + lo.double(), t.double()), what
+    assert _is_bf16_exact(ffx.a) != _is_bf16_exact(ffx.w)
+    wide = {"a_wide": ffx.a, "w_wide": ffx.w}[ffx.name]
+    assert not _is_bf16_exact(wide)
+    lo_fill = (ce.split_bf16(wide)[1] != 0).float().mean().item()
+    assert lo_fill > 0.2, lo_fill
+    mag = (ffx.a.double().abs() @ ffx.w.double().abs().t() + ffx.b.double().abs()).max().item() / ffx.u
+    ce.units(ffx.b, ffx.u)
+    ce.units(ce.fc1_reference64(ffx), ffx.u)
+    print(f"{ffx.name}: lo nonzero {100 * lo_fill:.0f} %, sum|a||w| + |b| {mag:.0f} units (worst case {ffx.bound_units:.0f})")
+    assert mag <= ffx.bound_units < 2**24
+    assert ffx.b.abs().max().item() / ffx.u <= 2**20
+
+
+def test_fc1_reference_is_exact_in_any_order(ffx):
+    """The fp64 result survives the cast to fp32, about half of it survives the ReLU, and the fp32
+    three-term emulation equals it bit for bit with k in its natural order and in a random order
+    (44 rows: the emulation is 3 * 4096 element-wise steps)."""
+    ref64 = ce.fc1_reference64(ffx)
+    assert torch.equal(ref64.float().double(), ref64)
+    nz = (ref64 != 0).double().mean().item()
+    assert 0.35 <= nz <= 0.65, nz
+    assert ref64.unique().numel() >= 1000
+    part = ce.fc1_fixture(ffx.name, M=44)
+    want = ref64[:44].float().view(torch.int32)
+    assert torch.equal(ce.fc1_reference64(part).float().view(torch.int32), want)  # smaller shapes are prefixes
+    for order_seed in (None, 13):
+        emu = ce.emulate_fc1_fp32(part, order_seed)
+        assert emu.dtype == torch.float32
+        assert torch.equal(emu.view(torch.int32), want), (ffx.name, order_seed)
+
+
+def test_fc1_k_prefixes_are_not_degenerate():
+    """The GPU test also runs K = 32, 64 and 96: there too about half the outputs survive the ReLU."""
+    for name in ce.FC1_NAMES:
+        for M, N, K in ((1, 256, 32), (255, 256, 64), (257, 512, 96)):
+            ref = ce.fc1_reference64(ce.fc1_fixture(name, M, N, K))
+            nz = (ref != 0).double().mean().item()
+            assert 0.3 <= nz <= 0.7, (name, M, N, K, nz)

@@ -10,8 +10,10 @@ stream, rows past M dropped by the descriptor's range check).
   ``test_cifar_fc1_x3_kernel`` against fp64 torch;
 * an adversarial A (bf16 rounding ties on even and odd upper halves, their
   neighbours, +-0, zero low halves, magnitudes 2^-100..2^100): lean is bitwise
-  staggered, i.e. the packed split equals the scalar split; and the blocked
-  encoding of the same values decodes to torch's ``split_bf16`` hi + lo;
+  staggered, i.e. the packed split equals the scalar split; through a W that
+  selects one element per output, each arm's split is bitwise torch's
+  ``split_bf16`` hi + lo; and the blocked encoding of the same values decodes
+  to the same;
 * race screen: 20 launches of lean on one input, every output bitwise the first."""
 import numpy as np
 import pytest
@@ -168,6 +170,35 @@ def test_fc1_lean_adversarial_split(sched):
     assert bool(torch.isfinite(outs["lean"][:M]).all())
     assert bool((outs["lean"][M:] == SENTINEL).all())
     assert torch.equal(_bits(outs["lean"]), _bits(outs["staggered"]))
+
+
+@pytest.mark.parametrize("split_in", [0, 1])
+def test_fc1_split_matches_torch_split(split_in, sched):
+    """The split of A inside the kernel (fp32 A; the packed one on lean, the scalar one on
+    staggered) or in ``encode_boundary`` (blocked A) against torch's ``split_bf16``, with no other arm
+    as the reference: W is bf16-exact with one nonzero per row, +1 at column n for n < 256 and -1 at
+    column n - 256 for n >= 256, and the bias is zero, so output (m, n) is relu(+-fl(hi + lo)) of one
+    element of A and every element is covered once with each sign.  0.0 is added to both sides first:
+    the sign of a zero is not asserted (the accumulator starts at +0 and takes 255 zero products)."""
+    from distributed_neural_networks_amd.ops.cifar import FC1_SCHED, encode_boundary, split_bf16
+    M, N, K = 300, 512, 256
+    a = _adv()[:, :K].contiguous()
+    assert bool(torch.isfinite(a).all())
+    w = torch.zeros(N, K, device=DEV)
+    w[torch.arange(256), torch.arange(256)] = 1.0
+    w[torch.arange(256, 512), torch.arange(256)] = -1.0
+    wh, wl = split_bf16(w)
+    assert torch.equal(wh.float(), w) and not bool(wl.float().any())
+    hi, lo = split_bf16(a)
+    s = hi.float() + lo.float()
+    want = torch.relu(torch.cat([s, -s], dim=1)) + 0.0
+    a_in = encode_boundary(a) if split_in else a
+    for name in FC1_SCHED:
+        sched(name)
+        out = _launch(a_in, K, wh, wl, K, torch.zeros(N, device=DEV), M, N, K, split_in)
+        torch.cuda.synchronize()
+        assert bool((out[M:] == SENTINEL).all()), name
+        assert torch.equal(_bits(out[:M] + 0.0), _bits(want)), name
 
 
 def test_boundary_encoding_matches_torch_split():

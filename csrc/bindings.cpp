@@ -144,6 +144,14 @@ PYBIND11_MODULE(_dnn_hip, m) {
   }, py::arg("x"), py::arg("out"), py::arg("w1h"), py::arg("w1l"), py::arg("b1"), py::arg("w2h"), py::arg("w2l"),
         py::arg("b2"), py::arg("B"), py::arg("grid"), py::arg("st"), py::arg("split_out") = 0,
         py::arg("w1h32") = 0, py::arg("w1l32") = 0);
+  m.def("cifar_stage0_x3_u8", [](u64 x, u64 table, u64 out, u64 w1h32, u64 w1l32, u64 b1, u64 w2h, u64 w2l, u64 b2,
+                                 int B, int grid, u64 st, int split_out) {
+    return dnn_cifar_stage0_x3_u8(reinterpret_cast<const unsigned char*>(static_cast<uintptr_t>(x)),
+                                  reinterpret_cast<const unsigned*>(static_cast<uintptr_t>(table)), FP(out), CP(w1h32),
+                                  CP(w1l32), CFP(b1), CP(w2h), CP(w2l), CFP(b2), B, grid, ST(st), split_out);
+  }, py::arg("x"), py::arg("table"), py::arg("out"), py::arg("w1h32"), py::arg("w1l32"), py::arg("b1"),
+        py::arg("w2h"), py::arg("w2l"), py::arg("b2"), py::arg("B"), py::arg("grid"), py::arg("st"),
+        py::arg("split_out") = 0);
   m.def("cifar_s0_set_conv1", [](int v) { return dnn_cifar_s0_set_conv1(v); });
   m.def("cifar_s0_get_conv1", []() { return dnn_cifar_s0_get_conv1(); });
   m.def("cifar_s0_set_wide_store", [](int on) { return dnn_cifar_s0_set_wide_store(on); });

@@ -87,6 +87,12 @@ int dnn_cifar_set_v4_pt(int pt);
 int dnn_cifar_stage0_x3(const float* x, float* out, const void* w1h, const void* w1l, const float* b1, const void* w2h,
                         const void* w2l, const float* b2, int B, int grid, hipStream_t st, int split_out = 0,
                         const void* w1h32 = nullptr, const void* w1l32 = nullptr);
+// uint8 NHWC input (B,32,32,3) normalised by table (uint32 [3][256]: bf16 hi bits low, lo bits high); K = 32
+// conv1 arm only.  Negative = rejected, nothing launched: -1 null table / weights, -2 conv1 switch on K = 48,
+// -3 x or table not 4-byte aligned.
+int dnn_cifar_stage0_x3_u8(const unsigned char* x, const unsigned* table, float* out, const void* w1h32,
+                           const void* w1l32, const float* b1, const void* w2h, const void* w2l, const float* b2, int B,
+                           int grid, hipStream_t st, int split_out = 0);
 int dnn_cifar_s0_set_conv1(int v);
 int dnn_cifar_s0_get_conv1();
 int dnn_cifar_s0_set_wide_store(int on);

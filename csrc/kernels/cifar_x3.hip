@@ -54,6 +54,11 @@
 //    (mod 32) is, with 8, the only pitch class for which {24 r + 3 c} are 32
 //    distinct banks (searched over all pitches >= 51 dwords).  The pooled conv1
 //    planes, their swizzle and the consumers are the same in both arms.
+//    uint8 input (template parameter IN = 1, dnn_cifar_stage0_x3_u8; K = 32
+//    producer only): the image arrives as (B,32,32,3) bytes and is normalised
+//    by a [3][256] table of packed bf16 hi/lo halves, copied into LDS behind
+//    the planes (116,480 B); the planes come out bit-identical to the fp32
+//    input's (see at the kernel).
 //  * cifar_fc1_x3_kernel: fc1 + bias + ReLU on the fp32 boundary tensor, the
 //    split done in registers while staging A (no split copy in HBM): 256x256x32
 //    tiles, 8 waves of 128x64, per k32 step 3 x 32 mfma_f32_16x16x32_bf16 per
@@ -142,6 +147,17 @@ template <int C1>
 __device__ __forceinline__ constexpr int lds_bytes() {  // 126464 (C1 = 0), 113408 (C1 = 1)
   return 4 * xpl<C1>() + 4 * A1PL;
 }
+// IN: input kind.  0: fp32 NCHW (B,3,32,32); 1: uint8 NHWC (B,32,32,3), normalised by a table
+// uint32 [3 channels][256 byte values], bf16 hi bits in the low half and bf16 lo bits in the high
+// half of an entry: what split2<true> gives for the normalised float ("uint8 input" at the kernel).
+constexpr int TAB_BYTES = 3 * 256 * 4;
+struct U8Input {
+  const unsigned char* x;
+  const uint32_t* table;
+};
+template <int IN>
+using s0_input_t = std::conditional_t<IN == 1, U8Input, const float* __restrict__>;
+
 template <int C1>
 __device__ __forceinline__ int xin_off(int k, int lo) {
   return ((k & 1) * 2 + lo) * xpl<C1>();
@@ -293,13 +309,23 @@ using namespace x3;
 // C2: conv2 consumer path.  0: v_mfma_f32_32x32x16_bf16 (32x8-pixel M tiles);
 // 1: v_mfma_f32_16x16x32_bf16 (4x4-pixel M tiles, 16-B stores only), the default:
 // the same MFMA cycles, a higher clock held under load (docs/ARCHITECTURE.md §2).
-template <bool WIDE, bool SPLIT_OUT, int C2 = 0, int C1 = 0>
+// IN = 1, "uint8 input" (C1 = 1 only): x is the image as it exists, (B,32,32,3) bytes, and the
+// normalisation is a table lookup in the producer.  The channel-packed plane of a row is the
+// byte order of an HWC row (element 3x + c <-> byte 3x + c), so the 12 bytes a thread loads are
+// its 12 plane elements in order and the channel of byte i is i % 3.  The table sits in LDS
+// behind the planes (3,072 B, outside the zeroed region, complete before the barrier that ends
+// the zeroing); an entry already holds the hi and lo halves of split2<true>, so the planes are
+// bit-identical to those of IN = 0 fed the normalised floats and everything after them is the
+// same code.  Per thread and image: 3 dword loads instead of 3 float4, 12 ds_read_b32 (issued
+// together) and 12 v_perm_b32 instead of 6 split2.
+template <bool WIDE, bool SPLIT_OUT, int C2 = 0, int C1 = 0, int IN = 0>
 __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
-    const float* __restrict__ x, float* __restrict__ out, const bf16_t* __restrict__ w1h,
+    s0_input_t<IN> x, float* __restrict__ out, const bf16_t* __restrict__ w1h,
     const bf16_t* __restrict__ w1l, const float* __restrict__ b1, const bf16_t* __restrict__ w2h,
     const bf16_t* __restrict__ w2l, const float* __restrict__ b2, int B) {
+  static_assert(IN == 0 || C1 == 1, "uint8 input exists in the K = 32 producer only");
   constexpr int LDS_BYTES = lds_bytes<C1>();
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
+  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES + (IN ? TAB_BYTES : 0)];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool producer = wave < 4;
@@ -310,8 +336,10 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
 
   // every halo (input and pooled map) is zero for the whole launch; interiors are rewritten per image
   for (int i = tid; i < LDS_BYTES / 16; i += 512) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0, 0, 0, 0);
+  if constexpr (IN == 1)
+    for (int i = tid; i < TAB_BYTES / 4; i += 512) reinterpret_cast<uint32_t*>(smem + LDS_BYTES)[i] = x.table[i];
 
-  __syncthreads();  // halos zeroed before any image is staged
+  __syncthreads();  // halos zeroed (and the table in place) before any image is staged
 
   // The two roles run disjoint loops (wave-uniform branch, the same number of
   // barriers on both sides) so their resident operands never share live ranges:
@@ -372,7 +400,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       }
     };
 
-    if constexpr (C1 == 0) {
+    if constexpr (C1 == 0 && IN == 0) {
       bf16x8 w1hf[3], w1lf[3];
 #pragma unroll
       for (int s = 0; s < 3; ++s) {
@@ -455,7 +483,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
 #pragma unroll 1
         for (int t = rw; t < 32; t += 8) conv1_pair(t, t + 4, it);
       });
-    } else {
+    } else if constexpr (C1 == 1) {
       // conv1 with the 27 taps in K = 32 (see "conv1 on K = 32" in the header): per x parity a
       // resident weight set [par][k-step], B-operand k = 16*s + 8*h + 0..7
       bf16x8 w1hf[2][2], w1lf[2][2];
@@ -476,23 +504,51 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       // apart would collide, 48 do not): conflict-free ds_write_b64
       const int sj = rt & 7, r5 = rt >> 3;
       const int sy = (r5 & ~3) | ((r5 & 1) << 1) | ((r5 >> 1) & 1);
-      float4 pf[3];
+      // the input prefetch: three float4 (IN = 0) or three dwords of bytes (IN = 1)
+      std::conditional_t<IN == 1, uint32_t, float4> pf[3];
       auto load_img = [&](int k) {
-        const float* xb = x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072 + sy * 32 + sj * 4;
+        if constexpr (IN == 1) {  // bytes 12 sj .. 12 sj + 11 of row sy: pixels 4 sj .. 4 sj + 3, HWC
+          const unsigned char* xb = x.x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072 + sy * 96 + sj * 12;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) pf[c] = *reinterpret_cast<const float4*>(xb + c * 1024);
+          for (int c = 0; c < 3; ++c) pf[c] = *reinterpret_cast<const uint32_t*>(xb + 4 * c);
+        } else {
+          const float* xb = x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072 + sy * 32 + sj * 4;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) pf[c] = *reinterpret_cast<const float4*>(xb + c * 1024);
+        }
       };
       auto stage_img = [&](int k) {  // prefetch registers -> padded channel-packed hi / lo planes
         const int o = (sy + 1) * XP32 + 8 + 24 * sj;
         char* xh = smem + xin_off<C1>(k, 0) + o;
         char* xl = smem + xin_off<C1>(k, 1) + o;
         uint2 vh[3], vl[3];
-        split2<true>(pf[0].x, pf[1].x, vh[0].x, vl[0].x);
-        split2<true>(pf[2].x, pf[0].y, vh[0].y, vl[0].y);
-        split2<true>(pf[1].y, pf[2].y, vh[1].x, vl[1].x);
-        split2<true>(pf[0].z, pf[1].z, vh[1].y, vl[1].y);
-        split2<true>(pf[2].z, pf[0].w, vh[2].x, vl[2].x);
-        split2<true>(pf[1].w, pf[2].w, vh[2].y, vl[2].y);
+        if constexpr (IN == 1) {
+          // byte i is plane element i, channel i % 3: all 12 table reads first, then per pair of
+          // entries the hi dword (the two low halves) and the lo dword (the two high halves)
+          const char* tab = smem + LDS_BYTES;
+          uint32_t e[12];
+#pragma unroll
+          for (int i = 0; i < 12; ++i)
+            e[i] = *reinterpret_cast<const uint32_t*>(tab + (i % 3) * 1024 + ((pf[i >> 2] >> (8 * (i & 3))) & 0xffu) * 4);
+          uint32_t ph[6], pl[6];
+#pragma unroll
+          for (int i = 0; i < 6; ++i) {
+            ph[i] = __builtin_amdgcn_perm(e[2 * i + 1], e[2 * i], 0x05040100u);
+            pl[i] = __builtin_amdgcn_perm(e[2 * i + 1], e[2 * i], 0x07060302u);
+          }
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+            vh[i] = make_uint2(ph[2 * i], ph[2 * i + 1]);
+            vl[i] = make_uint2(pl[2 * i], pl[2 * i + 1]);
+          }
+        } else {
+          split2<true>(pf[0].x, pf[1].x, vh[0].x, vl[0].x);
+          split2<true>(pf[2].x, pf[0].y, vh[0].y, vl[0].y);
+          split2<true>(pf[1].y, pf[2].y, vh[1].x, vl[1].x);
+          split2<true>(pf[0].z, pf[1].z, vh[1].y, vl[1].y);
+          split2<true>(pf[2].z, pf[0].w, vh[2].x, vl[2].x);
+          split2<true>(pf[1].w, pf[2].w, vh[2].y, vl[2].y);
+        }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
           *reinterpret_cast<uint2*>(xh + 8 * i) = vh[i];
@@ -1321,17 +1377,17 @@ extern "C" int dnn_cifar_s0_set_conv1(int v) {
 
 extern "C" int dnn_cifar_s0_get_conv1() { return g_s0_conv1; }
 
-template <bool SPLIT_OUT, int C1>
-static int launch_stage0_x3(const float* x, float* out, const void* w1h, const void* w1l, const float* b1,
+template <bool SPLIT_OUT, int C1, int IN = 0>
+static int launch_stage0_x3(s0_input_t<IN> x, float* out, const void* w1h, const void* w1l, const float* b1,
                             const void* w2h, const void* w2l, const float* b2, int B, int grid, hipStream_t st) {
   if (g_s0_mfma == 1)
-    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT, 1, C1>), dim3(grid), dim3(512), 0, st, x, out,
+    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT, 1, C1, IN>), dim3(grid), dim3(512), 0, st, x, out,
                        (const bf16_t*)w1h, (const bf16_t*)w1l, b1, (const bf16_t*)w2h, (const bf16_t*)w2l, b2, B);
   else if (g_s0_wide_store)
-    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT, 0, C1>), dim3(grid), dim3(512), 0, st, x, out,
+    hipLaunchKernelGGL((cifar_stage0_x3_kernel<true, SPLIT_OUT, 0, C1, IN>), dim3(grid), dim3(512), 0, st, x, out,
                        (const bf16_t*)w1h, (const bf16_t*)w1l, b1, (const bf16_t*)w2h, (const bf16_t*)w2l, b2, B);
   else
-    hipLaunchKernelGGL((cifar_stage0_x3_kernel<false, SPLIT_OUT, 0, C1>), dim3(grid), dim3(512), 0, st, x, out,
+    hipLaunchKernelGGL((cifar_stage0_x3_kernel<false, SPLIT_OUT, 0, C1, IN>), dim3(grid), dim3(512), 0, st, x, out,
                        (const bf16_t*)w1h, (const bf16_t*)w1l, b1, (const bf16_t*)w2h, (const bf16_t*)w2l, b2, B);
   return (int)hipGetLastError();
 }
@@ -1351,6 +1407,24 @@ extern "C" int dnn_cifar_stage0_x3(const float* x, float* out, const void* w1h, 
   }
   return split_out ? launch_stage0_x3<true, 0>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st)
                    : launch_stage0_x3<false, 0>(x, out, w1h, w1l, b1, w2h, w2l, b2, B, grid, st);
+}
+
+// The same stage on uint8 NHWC input (B,32,32,3), normalised by ``table`` (uint32 [3][256]: bf16 hi
+// bits low, bf16 lo bits high).  K = 32 conv1 arm only.  Rejected (negative, nothing launched):
+// -1 a null table or K = 32 weight pointer, -2 the conv1 switch is on K = 48, -3 x or table not
+// 4-byte aligned (the kernel reads both as dwords).
+extern "C" int dnn_cifar_stage0_x3_u8(const unsigned char* x, const unsigned* table, float* out, const void* w1h32,
+                                      const void* w1l32, const float* b1, const void* w2h, const void* w2l,
+                                      const float* b2, int B, int grid, hipStream_t st, int split_out) {
+  if (B <= 0) return 0;
+  if (g_s0_conv1 != 1) return -2;
+  if (!table || !w1h32 || !w1l32) return -1;
+  if (((uintptr_t)x | (uintptr_t)table) & 3) return -3;
+  if (grid <= 0) grid = 256;
+  if (grid > B) grid = B;
+  const U8Input in{x, table};
+  return split_out ? launch_stage0_x3<true, 1, 1>(in, out, w1h32, w1l32, b1, w2h, w2l, b2, B, grid, st)
+                   : launch_stage0_x3<false, 1, 1>(in, out, w1h32, w1l32, b1, w2h, w2l, b2, B, grid, st);
 }
 
 // fc1 k-loop arm: 1 = staggered wave groups, 2 = lean (the same schedule with the packed split and

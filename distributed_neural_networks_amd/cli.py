@@ -86,6 +86,23 @@ def load_image(path: Optional[str], nid: str) -> torch.Tensor:
     return torch.randn(1, 3, 32, 32)
 
 
+def load_image_u8(path: Optional[str], nid: str) -> torch.Tensor:
+    """``load_image`` up to the bytes: the same open, convert and resize, returned as the
+    ``(1,32,32,3)`` uint8 image (config ``input_dtype: "uint8"``: the stage normalises it by
+    table); seeded random bytes on failure, after the same log lines."""
+    try:
+        from PIL import Image
+        img = Image.open(path).convert("RGB").resize((32, 32), Image.BILINEAR)
+        t = torch.from_numpy(np.array(img, dtype=np.uint8)).contiguous().unsqueeze(0)
+        log(f"[{nid}] Loaded input image '{path}', shape: {t.shape}")
+        return t
+    except FileNotFoundError:
+        log(f"[{nid}] Input image '{path}' not found. Using dummy data.")
+    except Exception as e:  # noqa: BLE001
+        log(f"[{nid}] Error loading image: {e}. Using dummy data.")
+    return torch.randint(0, 256, (1, 32, 32, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
+
+
 def make_prompt(ctx: NodeContext, prompt: Optional[str]) -> torch.Tensor:
     from .runtime.generate import make_prompts
     return make_prompts(ctx.pipeline, prompt)
@@ -184,6 +201,14 @@ def load_stage_weights(ctx: NodeContext, part: int, ranges, full_sd=None, device
     return sd, full_sd
 
 
+def _input_table(pipe):
+    """The config's normalisation as a (3,256) table (uint8 input only)."""
+    if pipe.input_dtype != "uint8":
+        return None
+    from .ops.cifar import make_input_table
+    return make_input_table(pipe.input_mean, pipe.input_std)
+
+
 def build_stage(ctx: NodeContext, part: int, ranges, device: torch.device, full_sd=None, args=None):
     from .runtime.stages import CifarHipStage, TorchStage
     pipe = ctx.pipeline
@@ -193,7 +218,7 @@ def build_stage(ctx: NodeContext, part: int, ranges, device: torch.device, full_
     fam = model_info(pipe.model).family
     if device.type == "cuda":
         if fam == "cifar":
-            st = CifarHipStage(sd, a, b, device)
+            st = CifarHipStage(sd, a, b, device, input_dtype=pipe.input_dtype, input_table=_input_table(pipe))
         else:
             from .runtime.transformer import build_device_stage
             n_seq, n_pos = kv_needs(ctx, args) if args is not None else (8, 1024)
@@ -210,7 +235,8 @@ def build_stage(ctx: NodeContext, part: int, ranges, device: torch.device, full_
                                     fp8_prefill=pipe.fp8_prefill, top_p=pipe.top_p, min_p=pipe.min_p)
     else:
         st = TorchStage(pipe.model, sd, a, b, first, last, device,
-                        sampling=(pipe.temperature, pipe.top_k, pipe.seed, pipe.top_p, pipe.min_p))
+                        sampling=(pipe.temperature, pipe.top_k, pipe.seed, pipe.top_p, pipe.min_p),
+                        input_dtype=pipe.input_dtype, input_table=_input_table(pipe))
     log(f"[{ctx.node_id}] Successfully loaded weights into stage {part} (layers [{a},{b}]) on {device}.")
     return st, full_sd
 
@@ -305,7 +331,7 @@ async def initiate(ctx: NodeContext, args, stage, fwd, fam) -> int:
     rows = ctx.pipeline.micro_batch_size * ctx.pipeline.num_microbatches if fam == "cifar" else 1
     met = getattr(getattr(args, "_servicer", None), "metrics", None)
     for r in range(args.num_requests):
-        x = cifar_request(args, nid, rows, r) if fam == "cifar" else make_prompt(ctx, args.prompt)
+        x = make_cifar_request(ctx.pipeline, args, nid, rows, r) if fam == "cifar" else make_prompt(ctx, args.prompt)
         t_req = time.perf_counter()
         log(f"[{nid}] Running model part {ctx.part_index}...")
         loop = asyncio.get_running_loop()
@@ -394,6 +420,23 @@ def cifar_request(args, nid: str, rows: int, tag: int) -> torch.Tensor:
     return x
 
 
+def cifar_request_u8(args, nid: str, rows: int, tag: int) -> torch.Tensor:
+    """``cifar_request`` as ``(rows,32,32,3)`` uint8 images: row 0 is ``--input_image``, rows
+    1.. are seeded random bytes."""
+    x = load_image_u8(args.input_image, nid)
+    if rows > 1:
+        g = torch.Generator().manual_seed(1000 + tag)
+        x = torch.cat([x, torch.randint(0, 256, (rows - 1, 32, 32, 3), dtype=torch.uint8, generator=g)])
+    return x
+
+
+def make_cifar_request(pipe, args, nid: str, rows: int, tag: int) -> torch.Tensor:
+    """Stage 0's request in the form the config's ``input_dtype`` asks for."""
+    if pipe.input_dtype == "uint8":
+        return cifar_request_u8(args, nid, rows, tag)
+    return cifar_request(args, nid, rows, tag)
+
+
 def _fmt(preds) -> str:
     p = preds.tolist() if hasattr(preds, "tolist") else list(preds)
     return str(p[0] if len(p) == 1 else p)
@@ -424,7 +467,7 @@ def run_colocated(ctx: NodeContext, args, device) -> int:
     if device.type == "cuda":
         cp.capture()
     for r in range(args.num_requests):
-        x = cifar_request(args, nid, mbs * M, r).to(device)
+        x = make_cifar_request(pipe, args, nid, mbs * M, r).to(device)
         preds = []
         for i in range(M):
             preds.append(cp(x[i * mbs:(i + 1) * mbs]).pred.clone())
@@ -534,7 +577,7 @@ def _cifar_stream(ctx: NodeContext, args, stage, info, wd) -> int:
     if r == 0:
         # data parallel: replica k serves requests k, k+R, k+2R, ... (the tag keeps the global number)
         for req in range(ctx.replica, args.num_requests, pipe.replicas):
-            x = cifar_request(args, nid, mbs * M, req).to(dev)
+            x = make_cifar_request(pipe, args, nid, mbs * M, req).to(dev)
             fp.run_request(x, mbs, M, tag=req)
         fp.stop()
     else:

@@ -13,7 +13,8 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
   top level ``model``, ``dtype``, ``transport``, ``micro_batch_size``,
   ``num_microbatches``, ``seq_len``, ``decode_steps``, ``prompt_len``, ``temperature``, ``top_k``,
   ``top_p``, ``min_p``, ``seed``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
-  ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``; per node
+  ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``input_dtype``, ``input_mean``,
+  ``input_std`` (CIFAR: stage 0 takes uint8 images and normalises them by table); per node
   ``layers: [start, end]`` (inclusive, as in
   ``partitions/gpt_model_parts.py:12``) and ``device``.
 
@@ -83,6 +84,9 @@ class PipelineConfig:
     heartbeat_timeout_s: float = 15.0         # parallel/watchdog.py: peer declared dead after this
     stall_timeout_s: Optional[float] = None   # parallel/watchdog.py: abort when this rank stops progressing
     replicas: int = 1                         # data-parallel copies of the whole pipeline (rccl / gloo)
+    input_dtype: str = "fp32"                 # CIFAR stage 0 input: "fp32" (B,3,32,32) or "uint8" (B,32,32,3) images
+    input_mean: Tuple[float, float, float] = (0.5, 0.5, 0.5)  # uint8 input: per-channel Normalize mean ...
+    input_std: Tuple[float, float, float] = (0.5, 0.5, 0.5)   # ... and std (after the division by 255)
     raw: Dict[str, Any] = field(default_factory=dict)
 
     def stage(self, part_index: int) -> NodeSpec:
@@ -220,6 +224,20 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
     mp = cfg.get("min_p", 0.0)
     if not isinstance(mp, (int, float)) or isinstance(mp, bool) or not 0 <= mp < 1:
         raise ConfigError(f"ERROR: 'min_p' must be in [0, 1), got {mp!r}")
+    idt = cfg.get("input_dtype", "fp32")
+    if idt not in ("fp32", "uint8"):
+        raise ConfigError(f"ERROR: 'input_dtype' must be 'fp32' or 'uint8', got {idt!r}")
+    if idt == "uint8" and model != "cifar10":
+        raise ConfigError(f"ERROR: 'input_dtype' 'uint8' exists for model 'cifar10' only, got model '{model}'")
+    norm = {}
+    for key in ("input_mean", "input_std"):
+        v = cfg.get(key, [0.5, 0.5, 0.5])
+        if (not isinstance(v, (list, tuple)) or len(v) != 3
+                or any(not isinstance(e, (int, float)) or isinstance(e, bool) for e in v)):
+            raise ConfigError(f"ERROR: '{key}' must be three numbers (one per channel), got {v!r}")
+        norm[key] = tuple(float(e) for e in v)
+    if any(e == 0 for e in norm["input_std"]):
+        raise ConfigError(f"ERROR: 'input_std' must be nonzero in every channel, got {cfg.get('input_std')!r}")
     ret = cfg.get("return_to_node_id")
     if ret is not None and transport in DIST_TRANSPORTS:
         rn = next((n for n in nodes if n.id == ret), None)
@@ -239,7 +257,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         comm_timeout_s=float(cfg.get("comm_timeout_s", 300.0)),
         heartbeat_timeout_s=float(cfg.get("heartbeat_timeout_s", 15.0)),
         stall_timeout_s=(None if cfg.get("stall_timeout_s") is None else float(cfg["stall_timeout_s"])),
-        replicas=int(reps), raw=cfg)
+        replicas=int(reps), input_dtype=idt, input_mean=norm["input_mean"], input_std=norm["input_std"], raw=cfg)
 
 
 def resolve_node(cfg: Dict[str, Any], node_id: str, path: str = "<config>", replica: int = 0) -> NodeContext:

@@ -270,12 +270,109 @@ def decode_boundary(h: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
     return out
 
 
+# ---------------------------------------------------------------------------
+# uint8 input.  A CIFAR image exists as (32,32,3) bytes; its normalisation is a
+# per-channel function of a byte, so it is a (3,256) table, and the table *is*
+# the definition of the transform.  The fp32 stage-0 kernel looks the bytes up
+# while it stages them (cifar_x3.hip, "uint8 input"): 3 KiB/img instead of 12.
+# ---------------------------------------------------------------------------
+INPUT_DTYPES = ("fp32", "uint8")
+
+
+def make_input_table(mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)) -> torch.Tensor:
+    """``(3,256)`` fp32 CPU tensor: entry ``[c][b]`` is byte ``b`` of channel ``c`` after
+    ``ToTensor`` and ``Normalize(mean, std)``, in their fp32 arithmetic
+    (``(b / 255 - mean[c]) / std[c]``; ``cli.load_image`` computes the same bits)."""
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError(f"input table: mean and std need three entries each, got {mean!r}, {std!r}")
+    if any(float(s) == 0.0 for s in std):
+        raise ValueError(f"input table: std must be nonzero, got {std!r}")
+    b = torch.arange(256, dtype=torch.float32).div(255)
+    m = torch.tensor([float(v) for v in mean], dtype=torch.float32).view(3, 1)
+    s = torch.tensor([float(v) for v in std], dtype=torch.float32).view(3, 1)
+    return ((b.view(1, 256) - m) / s).contiguous()
+
+
+def _check_table(table: torch.Tensor) -> None:
+    if tuple(table.shape) != (3, 256) or table.dtype != torch.float32:
+        raise ValueError(f"input table: expected (3,256) fp32, got {table.dtype} {tuple(table.shape)}")
+
+
+def pack_input_table(table: torch.Tensor, device) -> torch.Tensor:
+    """``(3,256)`` fp32 -> ``(3,256)`` int32 on ``device``, the kernel's form: the low 16 bits
+    of an entry are the bf16 bits of ``hi = bf16(t)``, the high 16 bits those of
+    ``lo = bf16(t - hi)`` (``split_bf16``), exactly what the kernel's ``split2<true>`` gives
+    for the float ``t``.  Entries are expected to be 0 or of magnitude >= 2^-100: the residue
+    of a smaller one is denormal, and denormal residues are not part of the contract."""
+    _check_table(table)
+    hi, lo = split_bf16(table.detach().cpu())
+    hb = hi.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    lb = lo.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    packed = hb | (lb << 16)  # int32 wraps: bit 31 is lo's sign
+    return packed.to(torch.int32).to(device).contiguous()
+
+
+def normalize_u8(x_u8: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """``(B,32,32,3)`` uint8 -> ``(B,3,32,32)`` fp32 by gather from the ``(3,256)`` fp32
+    ``table``: the torch mirror of the kernel's lookup (CPU path, tests)."""
+    _check_table(table)
+    if x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or tuple(x_u8.shape[1:]) != (32, 32, 3):
+        raise ValueError(f"normalize_u8: expected uint8 (B,32,32,3), got {x_u8.dtype} {tuple(x_u8.shape)}")
+    t = table.to(x_u8.device)
+    idx = x_u8.permute(0, 3, 1, 2).long()  # (B,3,32,32)
+    out = torch.empty(idx.shape, dtype=torch.float32, device=x_u8.device)
+    for c in range(3):
+        out[:, c] = t[c][idx[:, c]]
+    return out
+
+
+def _stage0_u8(x: torch.Tensor, w: CifarStage0Weights, table: Optional[torch.Tensor], out: Optional[torch.Tensor],
+               grid: int, split: int) -> torch.Tensor:
+    """The uint8 arm of ``stage0_forward``: every rejection is raised before the launch."""
+    if w.precision != "fp32":
+        raise ValueError("stage0: uint8 input exists for the fp32 precision only (the bf16 kernel has no table path)")
+    if table is None:
+        raise ValueError("stage0: uint8 input needs a packed input table (pack_input_table(make_input_table(), device))")
+    if table.dtype != torch.int32 or tuple(table.shape) != (3, 256) or not table.is_contiguous() \
+            or table.device != x.device:
+        raise ValueError(f"stage0: the input table must be a packed (3,256) int32 tensor on {x.device} "
+                         f"(pack_input_table), got {table.dtype} {tuple(table.shape)} on {table.device}")
+    if x.dim() != 4 or tuple(x.shape[1:]) != (32, 32, 3):
+        raise ValueError(f"stage0: uint8 input must be NHWC (B,32,32,3), got {tuple(x.shape)}"
+                         + (" (NCHW: permute(0,2,3,1) first)" if tuple(x.shape[1:]) == (3, 32, 32) else ""))
+    if not x.is_contiguous():
+        raise ValueError("stage0: uint8 input must be contiguous")
+    if x.data_ptr() % 4:
+        raise ValueError(f"stage0: uint8 input must be 4-byte aligned (the kernel loads dwords), "
+                         f"data_ptr {x.data_ptr():#x} is misaligned")
+    if lib().cifar_s0_get_conv1() != STAGE0_CONV1["k32"]:
+        raise ValueError("stage0: uint8 input exists on the k32 conv1 arm only; the conv1 switch is on k48 "
+                         "(set_stage0_conv1('k32'))")
+    B = x.shape[0]
+    if out is None:
+        out = torch.empty((B, 4096), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (B, 4096) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("stage0: bad output buffer")
+    rc = lib().cifar_stage0_x3_u8(ptr(x), ptr(table), ptr(out), ptr(w.w1h32), ptr(w.w1l32), ptr(w.b1), ptr(w.w2h),
+                                  ptr(w.w2l), ptr(w.b2), B, grid, stream_ptr(), split)
+    if rc < 0:  # the library's own rejections, for a caller that raced the checks above
+        why = {-1: "a null table or weight pointer", -2: "the conv1 switch is on k48", -3: "misaligned input or table"}
+        raise ValueError(f"stage0: uint8 launch rejected: {why.get(rc, rc)}")
+    check(rc, "cifar_stage0_x3_u8")
+    return out
+
+
 def stage0_forward(x: torch.Tensor, w: CifarStage0Weights, out: Optional[torch.Tensor] = None,
-                   grid: int = 0, boundary: str = "fp32") -> torch.Tensor:
+                   grid: int = 0, boundary: str = "fp32", table: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Units 0-1: x (B,3,32,32) fp32 contiguous -> (B,4096) fp32 (or bf16 in bf16 mode;
-    ``boundary="split"``: the blocked hi/lo encoding in the fp32 tensor)."""
+    ``boundary="split"``: the blocked hi/lo encoding in the fp32 tensor).  Or x (B,32,32,3)
+    uint8 contiguous with a 4-byte-aligned ``data_ptr`` and ``table`` = its packed
+    normalisation table (``pack_input_table``; fp32 precision, ``k32`` conv1 arm): the
+    result is bitwise that of the fp32 input ``normalize_u8(x, table)``."""
     split = _split_boundary(boundary, w.precision)
     grid = grid or STAGE0_GRID
+    if x.dtype == torch.uint8:
+        return _stage0_u8(x, w, table, out, grid, split)
     _check_act(x, (3, 32, 32), torch.float32, "stage0 input")
     B = x.shape[0]
     dt = act_dtype(w.precision)

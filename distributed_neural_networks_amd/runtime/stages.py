@@ -65,12 +65,18 @@ class CifarHipStage(StageCompute):
     boundary (default; what a reference peer expects over gRPC), or "split" —
     the blocked hi/lo encoding of the same 16 KiB (``ops/cifar.py``;
     bit-identical results, measured neutral end to end).  Both stages of a hop
-    must agree."""
+    must agree.
+
+    ``input_dtype`` "uint8" (first stage, fp32 precision): the stage takes the
+    images as they exist, ``(B,32,32,3)`` bytes, and the stage-0 kernel
+    normalises them by ``input_table`` (a ``(3,256)`` fp32 table, default
+    ``make_input_table()``: the reference's Normalize(0.5, 0.5)); the result is
+    bitwise that of the fp32 input ``normalize_u8(x, input_table)``."""
 
     SUPPORTED = {(0, 1), (2, 3), (0, 3), (0, 2), (2, 2), (3, 3)}
 
     def __init__(self, sd: Dict[str, torch.Tensor], start: int, end: int, device: torch.device,
-                 precision: str = "fp32", boundary: str = "fp32"):
+                 precision: str = "fp32", boundary: str = "fp32", input_dtype: str = "fp32", input_table=None):
         from ..ops import cifar as cops
         if (start, end) not in self.SUPPORTED:
             raise ValueError(f"HIP CIFAR backend supports unit ranges {sorted(self.SUPPORTED)}, got ({start},{end})")
@@ -86,12 +92,24 @@ class CifarHipStage(StageCompute):
         self.w0 = cops.pack_stage0(sd, self.device, precision) if start == 0 else None
         self.wh = cops.pack_head(sd, self.device, fc1=start <= 2 <= end, fc2=end == 3, precision=precision)
         self._scratch: Dict[int, Dict[str, torch.Tensor]] = {}
+        if input_dtype not in cops.INPUT_DTYPES:
+            raise ValueError(f"input_dtype must be one of {cops.INPUT_DTYPES}, got {input_dtype!r}")
+        # only a first stage sees images; the others ignore the pipeline-wide setting
+        self.input_dtype = input_dtype if self.first else "fp32"
+        self.input_table = None
+        if self.input_dtype == "uint8":
+            if precision != "fp32":
+                raise ValueError("uint8 input exists for the fp32 precision only (the bf16 kernel has no table path)")
+            self.input_table = cops.pack_input_table(cops.make_input_table() if input_table is None else input_table,
+                                                     self.device)
 
     def _boundary(self, unit: int):
         return ((cifar.FLAT_DIM if unit == 1 else 512), self.adt)
 
     def in_spec(self, batch):
         if self.first:
+            if self.input_dtype == "uint8":
+                return (batch, 32, 32, 3), torch.uint8
             return (batch, 3, 32, 32), torch.float32
         w, dt = self._boundary(self.start - 1)
         return (batch, w), dt
@@ -122,10 +140,13 @@ class CifarHipStage(StageCompute):
         buf = self._buf(B)
         h = x
         if self.first:
-            if h.dtype != torch.float32:
+            if self.input_dtype == "uint8":
+                if h.dtype != torch.uint8:
+                    raise ValueError(f"stage 0 was built for uint8 (B,32,32,3) input, got {h.dtype} {tuple(h.shape)}")
+            elif h.dtype != torch.float32:
                 h = h.float()
             h = self._cops.stage0_forward(h.contiguous(), self.w0, buf["mid"] if self.end >= 2 else out,
-                                          boundary=self.boundary)
+                                          boundary=self.boundary, table=self.input_table)
             if self.end == 1:
                 return h
         elif h.dtype != self.adt:
@@ -143,7 +164,7 @@ class TorchStage(StageCompute):
     """Golden torch module as a stage (CPU fp32 plumbing path / tests)."""
 
     def __init__(self, model: str, sd: Dict[str, torch.Tensor], start: int, end: int, first: bool, last: bool,
-                 device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0)):
+                 device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0), input_dtype: str = "fp32", input_table=None):
         from ..models import build_golden_stage
         # sampling = (temperature, top_k, seed) or (temperature, top_k, seed, top_p, min_p)
         if len(sampling) not in (3, 5):
@@ -166,9 +187,21 @@ class TorchStage(StageCompute):
         if self.nhwc:
             self.module = self.module.to(memory_format=torch.channels_last)
         self.dtype = dtype
+        # CIFAR first stage on uint8 (B,32,32,3) images: normalised by table before the module
+        if input_dtype not in ("fp32", "uint8"):
+            raise ValueError(f"input_dtype must be 'fp32' or 'uint8', got {input_dtype!r}")
+        self.input_dtype = input_dtype if (self.family == "cifar" and first) else "fp32"
+        if input_dtype == "uint8" and self.family != "cifar":
+            raise ValueError("uint8 input exists for the CIFAR family only")
+        self.input_table = None
+        if self.input_dtype == "uint8":
+            from ..ops.cifar import make_input_table
+            self.input_table = (make_input_table() if input_table is None else input_table).to(self.device)
 
     def in_spec(self, batch, seq: int = 0):
         if self.family == "cifar":
+            if self.input_dtype == "uint8":
+                return (batch, 32, 32, 3), torch.uint8
             return cifar.input_shape(self.start, batch), self.dtype
         info = model_info(self.model)
         if self.first:
@@ -235,6 +268,9 @@ class TorchStage(StageCompute):
     def forward(self, x, out=None):
         x = x.to(self.device)
         with torch.no_grad():  # no autograd graph: a third of the CPU conv stage's time
+            if self.input_dtype == "uint8":
+                from ..ops.cifar import normalize_u8
+                x = normalize_u8(x, self.input_table).to(self.dtype)
             if self.nhwc and x.dim() == 4:
                 x = x.contiguous(memory_format=torch.channels_last)
             y = self.module(x)

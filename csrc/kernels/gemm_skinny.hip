@@ -838,8 +838,16 @@ static int launch_skinny_cfg(const void* A, int lda_b, const float* sa, const vo
                              int ks, const float* colsum, float eps, hipStream_t st, const void* Wsh) {
   const int groups = (N + 16 * NT - 1) / (16 * NT) * (MS ? (M + 15) / 16 : 1);
   while (ks > 1 && kbytes / 64 < ks) ks >>= 1;
-  size_t smem = (size_t)ks * NT * MT * 64 * sizeof(f32x4);
-  if (NORM != NORM_NONE) smem += (size_t)ks * MT * 2 * 16 * sizeof(float);
+  auto lds = [&](int waves) {
+    size_t b = (size_t)waves * NT * MT * 64 * sizeof(f32x4);
+    if (NORM != NORM_NONE) b += (size_t)waves * MT * 2 * 16 * sizeof(float);
+    return b;
+  };
+  // a pinned wave count (dnn_gemm_set_skinny_pin): 8 waves on the 4 x 4-tile line would ask for
+  // 128 KiB of LDS, so the wave count halves until 64 KiB hold it; the table's own lines use 32 KiB
+  // and less and are not affected
+  while (ks > 1 && lds(ks) > (size_t)64 * 1024) ks >>= 1;
+  const size_t smem = lds(ks);
   float2* rso = (!F32 && !FP8 && ACT != ACT_SILU_MUL) ? g_rs_cur.out : nullptr;
   hipLaunchKernelGGL((gemm_skinny_kernel<ACT, F32, MT, NT, FP8, U, PIPE, NORM, W8, MS>), dim3(groups), dim3(64 * ks), smem,
                      st, (const uint8_t*)A, lda_b, sa, (const uint8_t*)W, ldw_b, sw, C, ldc, bias, (const bf16_t*)R,
@@ -890,6 +898,17 @@ static int launch_skinny(const void* A, int lda_b, const float* sa, const void* 
                       (g_skinny_pin.k == 0 || g_skinny_pin.k * 2 == kbytes);
   if (pinned) {
     const int pk = g_skinny_pin.ks;
+    // ids 1-4 hold all rows in one workgroup: 2 row tiles cover 32 rows, so 33..64 rows take the
+    // table's 4-tile sibling of the same line (rows 32.. were left unwritten before)
+    if (M > 32) {
+      switch (g_skinny_pin.id) {
+        case 1: CFG(4, 1, 2, false, pk);
+        case 2: CFG(4, 1, 8, false, pk);
+        case 3: CFG(4, 2, 2, false, pk);
+        case 4: CFG(4, 4, 2, false, pk);
+        default: break;
+      }
+    }
     switch (g_skinny_pin.id) {  // (MT, NT, U, PIPE) / M-split (NT, U, PIPE) of the table
       case 1: CFG(2, 1, 2, false, pk);
       case 2: CFG(2, 1, 8, false, pk);

@@ -195,6 +195,9 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const bf16_t* __rest
   const int wave_qmin = p0 + min(qrow0, T - 1);
   const int blk_qmax = p0 + min(qb * FA_QB + FA_QB - 1, T - 1);
   const int kv_end = min(min(kv_len, blk_qmax + 1), S);  // never read past the cache
+  // last row a key tile's tail is clamped to: of the chunk's qkv rows (QKV), else of the cache -- with
+  // kv_len > S (the overflow is dropped) row kv_len - 1 is the next head's first row, or past the allocation
+  const int kv_last = (QKV ? kv_len : min(kv_len, S)) - 1;
 
   const bf16_t* krow_new = nullptr;  // QKV: this sequence's new-key rows (position p0 + t = row b*T + t)
   const bf16_t* vrow_new = nullptr;
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const bf16_t* __rest
     for (int it = 0; it < NIT; ++it) {
       const int e = it * 256 + tid;
       const int key = e / CH, c = e % CH;
-      const int kk = min(kb0 + key, kv_len - 1);
+      const int kk = min(kb0 + key, kv_last);
       if (QKV && kk >= p0) {
         pk[it] = *reinterpret_cast<const i32x4*>(krow_new + (size_t)(kk - p0) * ldq + c * 8);
         pv[it] = *reinterpret_cast<const i32x4*>(vrow_new + (size_t)(kk - p0) * ldq + c * 8);
@@ -630,7 +633,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
         for (int j = 0; j < 8; ++j) qv[g][8 * h8 + j] = bf2f_s(pq[j]);
       }
   }
-  const int knew = own_new ? p_new - k0 : -1;  // split-relative index of the register-held key
+  // split-relative index of the register-held key (none: past every row)
+  const int knew = own_new ? p_new - k0 : 0x7fffffff;
   // q and the new key are bf16-exact (rounded after RoPE): pack them into bf16
   // pairs so a score is 4 v_dot2_f32_bf16 per lane instead of 8 converts + 8 FMAs.
   uint32_t qp[G][ELT / 2], nkp[ELT / 2];  // bf16 pairs, reinterpreted only at the dot2 call
@@ -837,11 +841,13 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
           wz[j] = (uint32_t)(uint16_t)vr[u + 1][2 * j] | ((uint32_t)(uint16_t)vr[u + 1][2 * j + 1] << 16);
         }
       }
-      if (FUSED && ka == knew) {
+      // the new key is the split's last (knew == n - 1): rows past it were clamped onto the stale cache row
+      // p_new, whose 0-weight product is NaN if that row holds NaN or Inf -- they take the register copy too
+      if (FUSED && ka >= knew) {
 #pragma unroll
         for (int j = 0; j < ELT / 2; ++j) wa[j] = nvp[j];
       }
-      if (FUSED && kz == knew) {
+      if (FUSED && kz >= knew) {
 #pragma unroll
         for (int j = 0; j < ELT / 2; ++j) wz[j] = nvp[j];
       }
@@ -970,7 +976,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_1p_kernel(const bf16_t* _
   bf16_t* kb = kc + ((size_t)b * Hkv + kvh) * S * HD + (size_t)k0 * HD;
   bf16_t* vb = vc + ((size_t)b * Hkv + kvh) * S * HD + (size_t)k0 * HD;
   const bool own_new = FUSED && p_new < S && p_new >= k0 && p_new < k1;
-  const int knew = own_new ? p_new - k0 : -1;
+  const int knew = own_new ? p_new - k0 : 0x7fffffff;  // none: past every row
   const int pr = min(p_new, S - 1);
 
   // ---- K: MFMA tiles t = wave + NW*i (lane loads key row t*16 + hj, dims
@@ -1196,11 +1202,12 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_1p_kernel(const bf16_t* _
         wa[j] = (uint32_t)(uint16_t)vr[u][2 * j] | ((uint32_t)(uint16_t)vr[u][2 * j + 1] << 16);
         wz[j] = (uint32_t)(uint16_t)vr[u + 1][2 * j] | ((uint32_t)(uint16_t)vr[u + 1][2 * j + 1] << 16);
       }
-      if (FUSED && ka_ == knew) {
+      // rows past the new key (knew == n - 1) were clamped onto the stale cache row: the register copy, as above
+      if (FUSED && ka_ >= knew) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) wa[j] = nvp[j];
       }
-      if (FUSED && kz == knew) {
+      if (FUSED && kz >= knew) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) wz[j] = nvp[j];
       }

@@ -244,6 +244,12 @@ PYBIND11_MODULE(_dnn_hip, m) {
                            reinterpret_cast<void*>(static_cast<uintptr_t>(part)), IP(hist), hist_ld);
   }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("out"), py::arg("f32in"), py::arg("st"),
      py::arg("out2") = 0, py::arg("pos_inc") = 0, py::arg("part") = 0, py::arg("hist") = 0, py::arg("hist_ld") = 0);
+  m.def("logit_penalties", [](u64 x, int ld, int M, int N, u64 cnt, int cnt_ld, u64 prev, float rep, float freq,
+                              float pres, u64 st) {
+    return dnn_logit_penalties(P(x), ld, M, N, reinterpret_cast<unsigned short*>(static_cast<uintptr_t>(cnt)), cnt_ld,
+                               CIP(prev), rep, freq, pres, ST(st));
+  }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("cnt"), py::arg("cnt_ld"), py::arg("prev"),
+     py::arg("rep"), py::arg("freq"), py::arg("pres"), py::arg("st"));
   m.def("quant_fp8_rows", [](u64 x, int ldx, u64 q, u64 scale, int M, int K, int kpad, u64 st, int split) {
     return dnn_quant_fp8_rows(CP(x), ldx, P(q), FP(scale), M, K, kpad, ST(st), split);
   }, py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("scale"), py::arg("M"), py::arg("K"), py::arg("kpad"),

@@ -136,6 +136,12 @@ int dnn_sample_rows(const void* x, int ld, int M, int N, int* out, float tempera
                     int* pos_inc = nullptr, int* hist = nullptr, int hist_ld = 0, int* thr_out = nullptr);
 int dnn_argmax_rows(const void* x, int ld, int M, int N, int* out, int f32in, hipStream_t st, int* out2 = nullptr,
                     int* pos_inc = nullptr, void* part = nullptr, int* hist = nullptr, int hist_ld = 0);
+// repetition / presence / frequency penalties in place on bf16 logits (penalties.hip): cnt = uint16 per
+// (row, entry), bit 15 "in the prompt", bits 0..14 times generated; prev (optional): the token each row
+// generated last, counted first.  -1: null x / cnt, ld or cnt_ld not a multiple of 8 or below N, buffers
+// not 16-byte aligned, rep not > 0, freq / pres not finite
+int dnn_logit_penalties(void* x, int ld, int M, int N, unsigned short* cnt, int cnt_ld, const int* prev, float rep,
+                        float freq, float pres, hipStream_t st);
 int dnn_quant_fp8_rows(const void* x, int ldx, void* q, float* scale, int M, int K, int kpad, hipStream_t st,
                        int split = 0);
 int dnn_gemm_fp8(const void* A, const float* sa, const void* W, const float* sw, void* C, int ldc, const float* bias,

@@ -232,10 +232,14 @@ def build_stage(ctx: NodeContext, part: int, ranges, device: torch.device, full_
                                     max_batch=n_seq, max_seq=n_pos, max_tokens=ntok,
                                     temperature=pipe.temperature, top_k=pipe.top_k, seed=pipe.seed,
                                     kv_dtype=pipe.kv_cache_dtype, kv_scale=pipe.kv_cache_scale,
-                                    fp8_prefill=pipe.fp8_prefill, top_p=pipe.top_p, min_p=pipe.min_p)
+                                    fp8_prefill=pipe.fp8_prefill, top_p=pipe.top_p, min_p=pipe.min_p,
+                                    repetition_penalty=pipe.repetition_penalty,
+                                    presence_penalty=pipe.presence_penalty,
+                                    frequency_penalty=pipe.frequency_penalty)
     else:
         st = TorchStage(pipe.model, sd, a, b, first, last, device,
-                        sampling=(pipe.temperature, pipe.top_k, pipe.seed, pipe.top_p, pipe.min_p),
+                        sampling=(pipe.temperature, pipe.top_k, pipe.seed, pipe.top_p, pipe.min_p,
+                                  pipe.repetition_penalty, pipe.presence_penalty, pipe.frequency_penalty),
                         input_dtype=pipe.input_dtype, input_table=_input_table(pipe))
     log(f"[{ctx.node_id}] Successfully loaded weights into stage {part} (layers [{a},{b}]) on {device}.")
     return st, full_sd

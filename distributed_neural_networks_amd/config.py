@@ -23,6 +23,7 @@ Nothing here touches torch, so it is cheap to import from the CLI and tests.
 from __future__ import annotations
 
 import json
+import math
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -78,6 +79,9 @@ class PipelineConfig:
     top_p: float = 1.0                        # nucleus: smallest head of the distribution with this mass (1 = off)
     min_p: float = 0.0                        # drop tokens below this fraction of the top probability (0 = off)
     seed: int = 0                             # sampling seed (counter-based RNG, reproducible)
+    repetition_penalty: float = 1.0           # > 0; seen (prompt or generated) tokens: logit / r if > 0 else * r (1 = off)
+    presence_penalty: float = 0.0             # subtracted once from the logit of every generated token (0 = off)
+    frequency_penalty: float = 0.0            # subtracted per time the token was generated (0 = off)
     rpc_timeout_s: Optional[float] = None     # per-hop SendTensor deadline (reference: none)
     health_timeout_s: float = 120.0           # readiness barrier before stage 0 sends
     comm_timeout_s: float = 300.0             # process-group (RCCL/gloo) op timeout
@@ -224,6 +228,20 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
     mp = cfg.get("min_p", 0.0)
     if not isinstance(mp, (int, float)) or isinstance(mp, bool) or not 0 <= mp < 1:
         raise ConfigError(f"ERROR: 'min_p' must be in [0, 1), got {mp!r}")
+    rp = cfg.get("repetition_penalty", 1.0)
+    if not isinstance(rp, (int, float)) or isinstance(rp, bool) or not (rp > 0 and math.isfinite(rp)):
+        raise ConfigError(f"ERROR: 'repetition_penalty' must be a finite number > 0, got {rp!r}")
+    pens = {}
+    for key in ("presence_penalty", "frequency_penalty"):
+        v = cfg.get(key, 0.0)
+        if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v):
+            raise ConfigError(f"ERROR: '{key}' must be a finite number, got {v!r}")
+        pens[key] = float(v)
+    if model == "cifar10":
+        for key, v, neutral in (("repetition_penalty", rp, 1), ("presence_penalty", pens["presence_penalty"], 0),
+                                ("frequency_penalty", pens["frequency_penalty"], 0)):
+            if v != neutral:
+                raise ConfigError(f"ERROR: '{key}' {v!r} exists for the generating models only, got model '{model}'")
     idt = cfg.get("input_dtype", "fp32")
     if idt not in ("fp32", "uint8"):
         raise ConfigError(f"ERROR: 'input_dtype' must be 'fp32' or 'uint8', got {idt!r}")
@@ -252,7 +270,8 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         prompt_len=cfg.get("prompt_len"), decode_steps=int(cfg.get("decode_steps", 0)),
         prefill_chunk=int(cfg.get("prefill_chunk", 0)),
         temperature=float(cfg.get("temperature", 0.0)), top_k=int(cfg.get("top_k", 0)), seed=int(cfg.get("seed", 0)),
-        top_p=float(tp), min_p=float(mp),
+        top_p=float(tp), min_p=float(mp), repetition_penalty=float(rp), presence_penalty=pens["presence_penalty"],
+        frequency_penalty=pens["frequency_penalty"],
         rpc_timeout_s=cfg.get("rpc_timeout_s"), health_timeout_s=float(cfg.get("health_timeout_s", 120.0)),
         comm_timeout_s=float(cfg.get("comm_timeout_s", 300.0)),
         heartbeat_timeout_s=float(cfg.get("heartbeat_timeout_s", 15.0)),

@@ -41,6 +41,9 @@ PER_FILE_FLAGS = {"cifar_fused.hip": ["-ffast-math"],
                   "attention.hip": ["-fno-honor-nans"] + NO_SLP,
                   # scalar fp32 reductions (probability masses) next to 32-bit VALU reads
                   "sample_filter.hip": NO_SLP,
+                  # the penalty arithmetic is bitwise its torch mirror: multiply and subtract stay
+                  # two roundings (no FMA)
+                  "penalties.hip": ["-ffp-contract=off"] + NO_SLP,
                   "gemm_skinny.hip": NO_SLP,
                   "gemm_bf16.hip": NO_SLP}
 

@@ -323,3 +323,36 @@ def sample_rows(logits: torch.Tensor, out: torch.Tensor, n: int, temperature: fl
                             float(top_p), float(min_p), int(seed) & 0xFFFFFFFF, ptr(step), stream_ptr(), ptr(also),
                             ptr(advance), ptr(hist), hist_ld, ptr(thr_out)), "sample_rows")
     return out
+
+
+def logit_penalties(logits: torch.Tensor, cnt: torch.Tensor, prev: Optional[torch.Tensor], rep: float, freq: float,
+                    pres: float, n: int) -> torch.Tensor:
+    """Repetition / presence / frequency penalties in place on the first ``n``
+    entries of every row of bf16 ``logits`` (penalties.hip;
+    ``runtime/sampling.apply_penalties_ref`` is the bitwise mirror).  ``cnt``
+    (int16 / uint16, >= M rows, >= n wide): per entry bit 15 = in the prompt,
+    bits 0..14 = times generated.  ``prev`` (int32 per row, or None): the token
+    each row generated last; its count goes up by one first (out-of-range
+    tokens are ignored)."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("logit_penalties: bf16 (M, >= n) logits with contiguous rows expected")
+    if cnt.dtype not in (torch.int16, torch.uint16) or cnt.dim() != 2 or cnt.stride(1) != 1:
+        raise TypeError("logit_penalties: int16 / uint16 (M, >= n) state with contiguous rows expected")
+    M = logits.shape[0]
+    if not 0 < n <= logits.shape[1]:
+        raise ValueError(f"logit_penalties: n = {n} outside the row width {logits.shape[1]}")
+    if cnt.shape[0] < M or cnt.shape[1] < n:
+        raise ValueError(f"logit_penalties: state {tuple(cnt.shape)} does not cover ({M}, {n})")
+    ld, cnt_ld = (logits.stride(0), cnt.stride(0)) if M > 1 else (logits.shape[1], cnt.shape[1])
+    if ld % 8 or cnt_ld % 8 or ld < n or cnt_ld < n or logits.data_ptr() % 16 or cnt.data_ptr() % 16:
+        raise ValueError("logit_penalties: rows must start 16-byte aligned (row strides multiples of 8, >= n)")
+    if prev is not None and (prev.dtype != torch.int32 or prev.numel() < M or not prev.is_contiguous()):
+        raise ValueError(f"logit_penalties: prev must be contiguous int32 with >= {M} entries")
+    rep, freq, pres = float(rep), float(freq), float(pres)
+    if not (rep > 0 and math.isfinite(rep)):
+        raise ValueError(f"logit_penalties: repetition penalty must be a finite number > 0, got {rep!r}")
+    if not (math.isfinite(freq) and math.isfinite(pres)):
+        raise ValueError(f"logit_penalties: frequency / presence penalties must be finite, got {freq!r}, {pres!r}")
+    check(lib().logit_penalties(x=ptr(logits), ld=ld, M=M, N=n, cnt=ptr(cnt), cnt_ld=cnt_ld, prev=ptr(prev), rep=rep,
+                                freq=freq, pres=pres, st=stream_ptr()), "logit_penalties")
+    return logits

@@ -60,6 +60,12 @@ def check_capacity(stages, n_seq: int, n_pos: int) -> None:
             raise ValueError(f"prompt + decode steps = {n_pos} exceeds the model's block_size {bs}")
 
 
+def penalties_on(pipe) -> bool:
+    """The config asks for a repetition / presence / frequency penalty: the last
+    stage then needs every prompt's token ids (``DecodeRing(forward_prompt_ids=)``)."""
+    return pipe.repetition_penalty != 1.0 or pipe.presence_penalty != 0.0 or pipe.frequency_penalty != 0.0
+
+
 def _sync(dev):
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
@@ -136,7 +142,7 @@ def run_generate_dist(ctx, args, stage, info, progress=None) -> int:
     if links.nxt is not None:
         links.nxt.send_header(KIND_DATA, B, T, steps)
     check_capacity([stage], *kv_capacity(pipe, T))
-    ring = DecodeRing([stage], links, S, M, B, progress=progress)
+    ring = DecodeRing([stage], links, S, M, B, progress=progress, forward_prompt_ids=penalties_on(pipe))
     pf, dec = _timed_generate(ring, prompts, T, steps, dev, pipe.prefill_chunk)
     if r == 0:
         nid = ctx.node_id + (f" replica {ctx.replica}" if getattr(pipe, "replicas", 1) > 1 else "")

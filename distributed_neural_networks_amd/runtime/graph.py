@@ -9,6 +9,7 @@ capture serves every decode step.
 """
 from __future__ import annotations
 
+import gc
 from typing import Callable, Optional
 
 import torch
@@ -32,10 +33,22 @@ class GraphedStep:
             if reset is not None:
                 reset()
             s.synchronize()
-            # thread-local capture: ProcessGroupNCCL's watchdog thread keeps
-            # polling its events while a multi-GPU rank captures its decode step
-            with torch.cuda.graph(self.graph, stream=s, pool=pool, capture_error_mode="thread_local"):
-                self.result = fn()
+            # A HIP graph destroyed by this thread while it captures is an error
+            # raised inside a destructor (the process aborts), and a discarded
+            # ring holds its graphs in reference cycles that only the cyclic
+            # collector frees: run it now (torch.cuda.graph no longer does) and
+            # keep it off for the capture.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                # thread-local capture: ProcessGroupNCCL's watchdog thread keeps
+                # polling its events while a multi-GPU rank captures its decode step
+                with torch.cuda.graph(self.graph, stream=s, pool=pool, capture_error_mode="thread_local"):
+                    self.result = fn()
+            finally:
+                if gc_was_on:
+                    gc.enable()
         torch.cuda.current_stream(self.device).wait_stream(s)
 
     def __call__(self):

@@ -136,6 +136,58 @@ def sample_ref(logits: torch.Tensor, temperature: float, top_k: int = 0, top_p: 
     return (ids, thr.reshape(M).to(torch.int32)) if return_thr else ids
 
 
+# ---------------------------------------------------------------------- penalties
+# Torch mirror of csrc/kernels/penalties.hip.  State: one int16 per (row,
+# vocabulary entry), bit 15 = P (the token occurs in the prompt), bits 0..14 =
+# g (times generated in this generation, the prefill's token included;
+# saturates at 0x7FFF).
+PEN_P = 0x8000
+PEN_G = 0x7FFF
+
+
+def penalty_state(prompt_ids: torch.Tensor, vocab: int) -> torch.Tensor:
+    """(B, vocab) int16 state of the (B, T) prompts: P set for every prompt token, g = 0."""
+    ids = prompt_ids.to(device="cpu", dtype=torch.int64)
+    st = torch.zeros((ids.shape[0], vocab), dtype=torch.int16)
+    st.scatter_(1, ids, torch.full(ids.shape, -0x8000, dtype=torch.int16))
+    return st
+
+
+def penalty_count(state: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+    """A new state with ``g + 1`` (saturating) at ``tokens[row]`` of every row; P
+    is kept and a token outside [0, vocab) is ignored."""
+    u = state.cpu().view(torch.int16).to(torch.int64) & 0xFFFF
+    tok = tokens.cpu().to(torch.int64).reshape(-1)
+    for r in range(u.shape[0]):
+        t = int(tok[r])
+        if 0 <= t < u.shape[1] and (int(u[r, t]) & PEN_G) != PEN_G:
+            u[r, t] += 1
+    return torch.where(u >= 0x8000, u - 0x10000, u).to(torch.int16)
+
+
+def apply_penalties_ref(logits: torch.Tensor, state: torch.Tensor, rep: float, freq: float,
+                        pres: float) -> torch.Tensor:
+    """The kernel's rule in torch fp32, operation by operation (so bitwise equal
+    to it): for an entry with P or g > 0, ``x = x / rep if x > 0 else x * rep``
+    (when rep != 1), then for g > 0 ``x = x - freq * g`` and ``x = x - pres``,
+    rounded to bf16; every other entry keeps its bf16 bits.  ``logits`` (M, N)
+    (rounded to bf16 first), ``state`` (M, >= N); returns bf16 on the CPU."""
+    xb = logits.detach().to(device="cpu", dtype=torch.bfloat16)
+    u = state.cpu().view(torch.int16)[:, :xb.shape[1]].to(torch.int64) & 0xFFFF
+    g = u & PEN_G
+    seen = u != 0
+    f32 = torch.float32
+    x = xb.to(f32)
+    if float(rep) != 1.0:
+        r = torch.tensor(float(rep), dtype=f32)
+        x = torch.where(seen, torch.where(x > 0, x / r, x * r), x)
+    gen = g > 0
+    y = x - torch.tensor(float(freq), dtype=f32) * g.to(f32)
+    y = y - torch.tensor(float(pres), dtype=f32)
+    x = torch.where(gen, y, x)
+    return torch.where(seen, x.to(torch.bfloat16), xb)
+
+
 def pick(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0,
          step: Optional[torch.Tensor] = None, top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
     """Greedy when temperature <= 0, else the Gumbel sample over the top-k /

@@ -306,8 +306,15 @@ class DecodeRing:
 
     def __init__(self, stages: Sequence, links: RingLinks, n_groups: int, M: int, B: int,
                  use_graphs: bool = True, record: bool = True, progress: Progress = None, lanes: int = 0,
-                 multi_step: int = -1):
-        """``lanes`` (one group, M > 1, GPU): the M microbatch steps of a round
+                 multi_step: int = -1, forward_prompt_ids: bool = False):
+        """``forward_prompt_ids`` (more than one group; every rank passes the
+        same value, it follows the config): a last stage with penalties
+        (``penalties_on``) needs the prompt's token ids, which only group 0
+        has, so before a microbatch's first prefill piece rank 0 sends its
+        (B, T) int32 ids down the stage links, the middle ranks pass them on
+        and the last rank marks them (``penalty_begin``).
+
+        ``lanes`` (one group, M > 1, GPU): the M microbatch steps of a round
         replay on this many HIP streams (0 = one stream, -1 = min(M, 4));
         scratch rows follow the KV rows (``TransformerStage.step``), so
         concurrent microbatches share no buffer.  Off by default: measured on
@@ -379,6 +386,13 @@ class DecodeRing:
                      if n_groups == 1 and tail and cap > 0 and dev.type == "cuda" else None)
         self.hist_base = [0] * M  # position of the first decode token of the current generation
         self.hist_n = [0] * M  # decode tokens recorded in hist since then
+        # last stage with repetition / presence / frequency penalties: its per-row state starts at the prompt
+        # (_prefill) and survives the capture runs through snapshots (capture)
+        self.pen = self.stages[-1] if self.last and getattr(self.stages[-1], "penalties_on", False) else None
+        self.forward_prompt_ids = bool(forward_prompt_ids) and n_groups > 1
+        if self.pen is not None and n_groups > 1 and not self.forward_prompt_ids:
+            raise ValueError("a last stage with penalties on a ring of several groups needs forward_prompt_ids=True "
+                             "on every rank (the prompt ids live on group 0)")
 
     # -- one microbatch through this rank's stages --------------------------
     def _run(self, x, m: int, T: int, out=None, advance=None):
@@ -495,9 +509,19 @@ class DecodeRing:
         if not self.last:
             out_pf = [torch.empty((B * C, d), dtype=out_dt, device=self.dev) for _ in range(2)]
         n_sent = 0
+        id_work: List[tuple] = []  # (work, tensor) of the prompt ids on their way down the stage links
         for m in range(self.M):
             if self.first:
                 ids = prompts[m].to(device=self.dev, dtype=torch.int32).contiguous()
+            elif self.forward_prompt_ids:
+                ids = torch.empty((B, T), dtype=torch.int32, device=self.dev)
+                self.links.prev.recv(ids)
+            if self.forward_prompt_ids and not self.last:
+                id_work.append((self.links.nxt.isend(ids), ids))
+            if self.pen is not None:
+                # the whole prompt is marked before its first token is sampled (chunked prefill and the
+                # fp8-KV calibration prefills included: each starts from the prompt alone)
+                self.pen.penalty_begin(m * B, ids)
             self._out_ready(m)
             for t0, Tc in pieces:
                 final = t0 + Tc == T
@@ -512,6 +536,8 @@ class DecodeRing:
                 with trace.span("prefill", "compute", mb=m, t0=t0):
                     y = self._run(x, m, Tc, out=(self.out[m] if self.last else out_pf[k][:B * Tc]))
                 self.pos[m].add_(Tc)
+                if self.pen is not None and not final:
+                    self.pen.penalty_forget(m * B, B)  # this piece's sample is discarded, never counted
                 if not self.last:
                     pf_work[k] = self.links.nxt.isend(out_pf[k][:B * Tc])
                     n_sent += 1
@@ -527,6 +553,8 @@ class DecodeRing:
         for w in pf_work:
             if w is not None:
                 w.wait()
+        for w, _ in id_work:
+            w.wait()
         if self.first and self.G > 1:
             self.pending = [True] * self.M  # every prompt's first token comes back over the back-edge
         self.steps_done = 0
@@ -540,11 +568,14 @@ class DecodeRing:
         for m in range(self.M):
             snap = self.pos[m].clone()
             cur = self.cur[m].clone() if self.first else None
+            pen = self.pen.penalty_snapshot(m * self.B, self.B) if self.pen is not None else None
             self._out_ready(m)
             self.graphs[m] = GraphedStep(lambda m=m: self._decode_body(m), self.dev, warmup=1)
             self.pos[m].copy_(snap)  # the warmup/capture runs advanced the position
             if cur is not None:
                 self.cur[m].copy_(cur)
+            if pen is not None:
+                self.pen.penalty_restore(pen)  # ... counted their tokens and overwrote the previous-token entries
         torch.cuda.synchronize(self.dev)
         self._capture_multi_step()
 
@@ -560,6 +591,8 @@ class DecodeRing:
         from .graph import GraphedStep
         snap = [p.clone() for p in self.pos]
         cur = [c.clone() for c in self.cur] if self.first else None
+        pen = ([self.pen.penalty_snapshot(m * self.B, self.B) for m in range(self.M)]
+               if self.pen is not None else None)
 
         def body():
             for _ in range(K):
@@ -571,6 +604,8 @@ class DecodeRing:
                 self.pos[m].copy_(snap[m])
                 if cur is not None:
                     self.cur[m].copy_(cur[m])
+                if pen is not None:
+                    self.pen.penalty_restore(pen[m])
         self.graph_k = GraphedStep(body, self.dev, warmup=1, reset=reset)
         self.graph_k_steps = K
         reset()  # the capture run advanced them again

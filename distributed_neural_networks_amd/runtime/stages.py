@@ -166,11 +166,23 @@ class TorchStage(StageCompute):
     def __init__(self, model: str, sd: Dict[str, torch.Tensor], start: int, end: int, first: bool, last: bool,
                  device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0), input_dtype: str = "fp32", input_table=None):
         from ..models import build_golden_stage
-        # sampling = (temperature, top_k, seed) or (temperature, top_k, seed, top_p, min_p)
-        if len(sampling) not in (3, 5):
-            raise ValueError(f"sampling: 3 or 5 entries expected, got {len(sampling)}")
+        # sampling = (temperature, top_k, seed[, top_p, min_p[, repetition, presence, frequency penalty]])
+        if len(sampling) not in (3, 5, 8):
+            raise ValueError(f"sampling: 3, 5 or 8 entries expected, got {len(sampling)}")
         self.temperature, self.top_k, self.seed = float(sampling[0]), int(sampling[1]), int(sampling[2])
-        self.top_p, self.min_p = (float(sampling[3]), float(sampling[4])) if len(sampling) == 5 else (1.0, 0.0)
+        self.top_p, self.min_p = (float(sampling[3]), float(sampling[4])) if len(sampling) >= 5 else (1.0, 0.0)
+        self.rep_pen, self.pres_pen, self.freq_pen = ((float(sampling[5]), float(sampling[6]), float(sampling[7]))
+                                                      if len(sampling) == 8 else (1.0, 0.0, 0.0))
+        import math
+        if not (self.rep_pen > 0 and math.isfinite(self.rep_pen)):
+            raise ValueError(f"repetition penalty must be a finite number > 0, got {sampling[5]!r}")
+        if not (math.isfinite(self.pres_pen) and math.isfinite(self.freq_pen)):
+            raise ValueError(f"presence / frequency penalties must be finite, got {sampling[6]!r}, {sampling[7]!r}")
+        self.penalties_on = bool(last) and (self.rep_pen != 1.0 or self.pres_pen != 0.0 or self.freq_pen != 0.0)
+        # penalty state per microbatch offset b0 (runtime/sampling.py mirror of the device state) and the
+        # token the rows generated last, counted by the next decode step
+        self._pen: Dict[int, torch.Tensor] = {}
+        self._pen_prev: Dict[int, Optional[torch.Tensor]] = {}
         self.model, self.start, self.end, self.first, self.last = model, start, end, first, last
         self.device = torch.device(device)
         self.family = model_info(model).family
@@ -224,6 +236,19 @@ class TorchStage(StageCompute):
     def act_dtype(self) -> torch.dtype:
         return self.dtype
 
+    def penalty_begin(self, b0: int, ids: torch.Tensor) -> None:
+        """Start a generation on cache rows [b0, b0 + B): the (B, T) prompt's
+        tokens are marked, nothing is counted yet (``TransformerStage.penalty_begin``)."""
+        from .sampling import penalty_state
+        if not self.penalties_on:
+            raise ValueError("penalty_begin: this stage has no penalties")
+        self._pen[b0] = penalty_state(ids, model_info(self.model).cfg.vocab_size)
+        self._pen_prev[b0] = None
+
+    def penalty_forget(self, b0: int, B: int) -> None:
+        """The sample of a prefill piece before the last one is no generated token."""
+        self._pen_prev[b0] = None
+
     @torch.no_grad()
     def step(self, x, pos, B: int, T: int, b0: int = 0, out=None, last_only: bool = True):
         """KV-cached transformer step (CPU golden path; same contract as
@@ -252,8 +277,20 @@ class TorchStage(StageCompute):
             from .sampling import pick
             logits = y[:, -1, :] if last_only else y.reshape(B * T, -1)
             step = pos if isinstance(pos, torch.Tensor) else torch.full((B,), p, dtype=torch.int32)
+            if self.penalties_on and last_only:
+                # as the device stage: a decode step counts the rows' previous token, then every sampled
+                # position's logits (rounded to bf16) take the penalties
+                from .sampling import apply_penalties_ref, penalty_count
+                if b0 not in self._pen:
+                    raise ValueError(f"penalties: no penalty_begin for cache rows at {b0}")
+                if T == 1 and self._pen_prev[b0] is not None:
+                    self._pen[b0] = penalty_count(self._pen[b0], self._pen_prev[b0])
+                logits = apply_penalties_ref(logits, self._pen[b0], self.rep_pen, self.freq_pen, self.pres_pen)
+                y = logits[:, None, :]
             pred = pick(y[:, -1, :], self.temperature, self.top_k, self.seed, step, top_p=self.top_p,
                         min_p=self.min_p).to(torch.int32)
+            if self.penalties_on and last_only:
+                self._pen_prev[b0] = pred.clone()
             if out is not None and last_only:
                 out.copy_(pred)
                 pred = out

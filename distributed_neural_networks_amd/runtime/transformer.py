@@ -83,7 +83,8 @@ class TransformerStage(StageCompute):
                  device, max_batch: int = 8, max_seq: int = 1024, max_tokens: Optional[int] = None,
                  fp8: bool = False, temperature: float = 0.0, top_k: int = 0, seed: int = 0,
                  kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
-                 top_p: float = 1.0, min_p: float = 0.0):
+                 top_p: float = 1.0, min_p: float = 0.0, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
         info = model_info(model)
         # fp8 weights, prefill (W8A8) activations: "e4m3" (default) = one e4m3
         # byte per activation, per-row scale, at the fp8 MFMA rate; "split" =
@@ -107,6 +108,19 @@ class TransformerStage(StageCompute):
             raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
         if not 0.0 <= self.min_p < 1.0:
             raise ValueError(f"min_p must be in [0, 1), got {min_p!r}")
+        # penalties (last stage): device state updated and applied by a launch of
+        # its own in front of the argmax / sampler (csrc/kernels/penalties.hip)
+        self.rep_pen, self.pres_pen, self.freq_pen = (float(repetition_penalty), float(presence_penalty),
+                                                      float(frequency_penalty))
+        if not (self.rep_pen > 0 and math.isfinite(self.rep_pen)):
+            raise ValueError(f"repetition_penalty must be a finite number > 0, got {repetition_penalty!r}")
+        if not (math.isfinite(self.pres_pen) and math.isfinite(self.freq_pen)):
+            raise ValueError(f"presence_penalty / frequency_penalty must be finite, got {presence_penalty!r}, "
+                             f"{frequency_penalty!r}")
+        self.penalties_on = bool(last) and (self.rep_pen != 1.0 or self.pres_pen != 0.0 or self.freq_pen != 0.0)
+        if self.penalties_on and max_seq >= 32768:
+            raise ValueError(f"penalties: max_seq {max_seq} >= 32768 (the 15-bit token count must not saturate "
+                             f"within a generation)")
         self.model, self.family, self.cfg = model, info.family, info.cfg
         self.start, self.end, self.first, self.last = start, end, first, last
         self.device = dev = torch.device(device)
@@ -373,6 +387,54 @@ class TransformerStage(StageCompute):
             self.buf_lnf = torch.empty((ntok, d), dtype=bf, device=dev)
             self.logits = torch.empty((ntok, self.Vpad), dtype=bf, device=dev)
             self.next_ids = torch.empty((ntok,), dtype=torch.int32, device=dev)
+        self.pen_state = self.pen_prev = None
+        if self.penalties_on:
+            # per KV row: the uint16 state of every vocabulary entry (bit 15 = in the prompt, bits 0..14 =
+            # times generated) and the token the row generated last (-1: none yet), which the next decode
+            # step's penalty launch counts
+            self.pen_state = torch.zeros((self.max_batch, self.Vpad), dtype=torch.int16, device=dev)
+            self.pen_prev = torch.full((self.max_batch,), -1, dtype=torch.int32, device=dev)
+
+    # ------------------------------------------------------------------ penalties
+    def penalty_begin(self, b0: int, ids: torch.Tensor) -> None:
+        """Start a generation on cache rows [b0, b0 + B): clear their state and
+        mark the tokens of the (B, T) prompt ``ids``.  Before the prompt's first
+        prefill piece (prefill is not the hot path: torch zero_ + scatter_)."""
+        if not self.penalties_on:
+            raise ValueError("penalty_begin: this stage has no penalties")
+        B = ids.shape[0]
+        if ids.dim() != 2 or b0 < 0 or b0 + B > self.max_batch:
+            raise ValueError(f"penalty_begin: ids {tuple(ids.shape)} at row {b0} outside the {self.max_batch} rows")
+        st = self.pen_state[b0:b0 + B]
+        st.zero_()
+        # clamped like the embedding's lookup: a bad id cannot index outside the row
+        idx = ids.to(device=self.device, dtype=torch.int64).clamp(0, self.V - 1)
+        st.scatter_(1, idx, -0x8000)
+        self.pen_prev[b0:b0 + B].fill_(-1)
+
+    def penalty_forget(self, b0: int, B: int) -> None:
+        """Drop the previous token of rows [b0, b0 + B): what a prefill piece
+        before the last one sampled is no generated token, and the next piece
+        may be one token long (a decode-shaped step, which counts it)."""
+        self.pen_prev[b0:b0 + B].fill_(-1)
+
+    def penalty_snapshot(self, b0: int, B: int):
+        """Copies of rows [b0, b0 + B) of the penalty state and of their
+        previous-token entries (graph capture runs the decode body for real:
+        ``DecodeRing.capture`` puts both back with ``penalty_restore``)."""
+        return b0, B, self.pen_state[b0:b0 + B].clone(), self.pen_prev[b0:b0 + B].clone()
+
+    def penalty_restore(self, snap) -> None:
+        b0, B, st, prev = snap
+        self.pen_state[b0:b0 + B].copy_(st)
+        self.pen_prev[b0:b0 + B].copy_(prev)
+
+    def _penalise(self, logits, b0: int, rows: int, T: int) -> None:
+        """The penalty launch of a ``last_only`` step on its ``rows`` = B logits
+        rows; a decode step first counts the rows' previous token."""
+        prev = self.pen_prev[b0:b0 + rows] if T == 1 else None
+        T_.logit_penalties(logits, self.pen_state[b0:b0 + rows], prev, self.rep_pen, self.freq_pen, self.pres_pen,
+                           self.V)
 
     def _lin(self, x, w, b, act=ACT_NONE, residual=None, out=None, ncols=None, w_shuf=None, ws=None, rs_out=None,
              mx_in=None):
@@ -511,7 +573,8 @@ class TransformerStage(StageCompute):
         else:
             rows, src, ldx = ntok, h, d
         logits = self.logits[r0:r0 + rows]
-        if self.fuse_norm and last_only and not self.temperature > 0:
+        pen = self.penalties_on and last_only
+        if self.fuse_norm and last_only and not self.temperature > 0 and not pen:
             # greedy: the head writes the logits and each workgroup's argmax
             # partials; one merge launch takes the ids and the step tail
             x_last = torch.as_strided(src, (rows, d), (ldx, 1))
@@ -532,6 +595,10 @@ class TransformerStage(StageCompute):
             else:
                 linear(lnf, self.w_head, None, out=logits[:, :self.V])
         nxt = self.next_ids[r0:r0 + rows]
+        if pen:
+            # penalised logits feed the unchanged argmax / sampler launches below (never the fused head, whose
+            # argmax comes from the unpenalised values)
+            self._penalise(logits, b0, rows, T)
         if self.temperature > 0 and last_only:
             if not T_.SAMPLE_FUSED_TAIL:  # the A/B baseline: sampler launch, then the ids copy (and the ring's tail launches)
                 if self.top_p < 1.0 or self.min_p > 0.0:
@@ -541,16 +608,24 @@ class TransformerStage(StageCompute):
                     T_.sample_topk(logits, nxt, self.V, self.temperature, self.top_k, self.seed, step=pos)
                 if out is not None:
                     out.copy_(nxt)
+                if pen:
+                    self.pen_prev[b0:b0 + rows].copy_(nxt)
                 return StageOutput(logits[:, :self.V], nxt)
             dst = out if out is not None else nxt
             also, adv, hist = _advance3(advance)
             T_.sample_rows(logits, dst, self.V, self.temperature, self.top_k, self.top_p, self.min_p, self.seed,
                            step=pos, also=also, advance=adv, hist=hist)
+            if pen:
+                self.pen_prev[b0:b0 + rows].copy_(dst)
             return StageOutput(logits[:, :self.V], dst)
         dst = out if (last_only and out is not None) else nxt
         also, adv, hist = _advance3(advance)
         part = self.amx_part[r0 * 2 * T_.ARGMAX_PART_PER_ROW:] if last_only else None
         T_.argmax_rows(logits, dst, n=self.V, also=also, advance=adv, part=part, hist=hist)
+        if pen:
+            # the rows' token in a stage-owned place (the caller's `out` may change between calls): the next
+            # decode step's penalty launch reads it from the same address on every graph replay
+            self.pen_prev[b0:b0 + rows].copy_(dst)
         return StageOutput(logits[:, :self.V], dst)
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None):
@@ -599,13 +674,15 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                        max_batch: int = 8, max_seq: int = 1024, max_tokens: Optional[int] = None,
                        temperature: float = 0.0, top_k: int = 0, seed: int = 0, kv_dtype: str = "bf16",
                        kv_scale: str = "calibrated", fp8_prefill: str = "e4m3", top_p: float = 1.0,
-                       min_p: float = 0.0):
+                       min_p: float = 0.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                       frequency_penalty: float = 0.0):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
     info = model_info(model)
     max_seq = min(max_seq, getattr(info.cfg, "block_size", getattr(info.cfg, "max_seq", max_seq)))
     return TransformerStage(model, sd, start, end, first, last, device, max_batch, max_seq, max_tokens, fp8,
                             temperature, top_k, seed, kv_dtype=kv_dtype, kv_scale=kv_scale, fp8_prefill=fp8_prefill,
-                            top_p=top_p, min_p=min_p)
+                            top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
 
 
 # ---------------------------------------------------------------------- smoke / golden check

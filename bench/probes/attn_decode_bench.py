@@ -2,9 +2,8 @@
 """Fused decode-attention microbenchmark (``attn_decode_qkv``: RoPE + KV write
 + split-K attention from the QKV projection rows): device time per launch as
 HIP-graph replays, per shape and split count, plus the bytes-per-second of the
-K/V stream, for both score paths (suffix ``m``: MFMA key tiles,
-the GQA default; none: DPP row reductions).  Shapes are the decode benches' (Llama-3 8B B=1 / B=32, GPT-2
-B=64 / B=256).
+K/V stream (scores on MFMA key tiles at GQA, DPP row reductions at MHA).
+Shapes are the decode benches' (Llama-3 8B B=1 / B=32, GPT-2 B=64 / B=256).
 
     python bench/probes/attn_decode_bench.py [--iters 50] [--splits 1,2,4,8,16]
 """
@@ -53,12 +52,10 @@ def main():
                "auto_splits": decode_splits(S, B, Hkv, G)}
         kv_bytes = 2 * B * Hkv * (pos + 1) * hd * 2
         ref = None
-        modes = {"": "0", "m": "1"}
-        for sp, mode in [(int(v), m) for v in args.splits.split(",") for m in modes]:
+        for sp in [int(v) for v in args.splits.split(",")]:
             sp = sp or res["auto_splits"]
             if sp < decode_splits(S, B, Hkv, G) and sp < res["auto_splits"]:
                 continue
-            os.environ["DNN_DECODE_MFMA"] = modes[mode]
             ws = torch.empty(B * Hkv * sp * G * (hd + 2), device=dev, dtype=torch.float32)
 
             def run():
@@ -82,7 +79,7 @@ def main():
             b.record()
             torch.cuda.synchronize()
             us = a.elapsed_time(b) / (5 * args.iters) * 1e3
-            key = f"s{sp}{mode}"
+            key = f"s{sp}"
             res[f"{key}_us"] = round(us, 2)
             res[f"{key}_GBs"] = round(kv_bytes / us / 1e3, 1)
             res[f"{key}_maxdiff"] = round(err, 4)

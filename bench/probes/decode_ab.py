@@ -25,15 +25,8 @@ def apply(switch: str, v: int) -> None:
         lib().gemm_set_res_prefetch(v)
     elif switch == "fold_norm":
         gemm.FOLD_NORM_PREFILL = bool(v)
-    elif switch == "kv8_u":  # fp8-KV decode attention rows in flight per thread (attention.hip KV8U)
-        os.environ["DNN_KV8_U"] = str(v)
     elif switch == "qkv_scatter":  # prefill c_attn straight into q / the KV caches (ops/gemm.py QKV_SCATTER)
         gemm.QKV_SCATTER = bool(v)
-    elif switch == "decode_splits":  # decode-attention split count (0 = the heuristic), read at stage build
-        if v:
-            os.environ["DNN_DECODE_SPLITS"] = str(v)
-        else:
-            os.environ.pop("DNN_DECODE_SPLITS", None)
     elif switch == "stream_fold":  # stream GEMM split-K combine: 1 in the launch, 0 separate reduce launch
         gemm.set_stream_gemm(1, 0, v)
     elif switch == "stream":  # decode stream GEMM: 0 off, 1 where it measured faster, 2 forced (gemm_stream.h)
@@ -42,14 +35,10 @@ def apply(switch: str, v: int) -> None:
         os.environ["DNN_DECODE_1P"] = str(v)
     elif switch == "decode_1p_kf":  # one-pass decode attention: K/V loads issued before q (attention.hip KF)
         os.environ["DNN_DECODE_1P_KF"] = str(v)
-    elif switch == "flash_db":  # flash prefill with double-buffered K/V LDS (attention.hip DNN_FLASH_DB)
-        os.environ["DNN_FLASH_DB"] = str(v)
     elif switch == "epi_pre":  # decode GEMM epilogue operands issued with the first loads (gemm_oneshot.h / skinny)
         lib().gemm_set_epi_prefetch(v)
     elif switch == "os_lds_floor":  # one-shot launch LDS floor in bytes (gemm_skinny.hip g_os_lds_floor; 0 = own size)
         lib().gemm_set_oneshot_lds_floor(v)
-    elif switch == "flash_pipe":  # hd-64 flash prefill software pipeline (attention.hip DNN_FLASH_PIPE)
-        os.environ["DNN_FLASH_PIPE"] = str(v)
     elif switch == "rowstats_r":  # prefill row statistics rows per wave (norm_embed.hip dnn_row_stats)
         os.environ["DNN_ROWSTATS_R"] = str(v)
     elif switch == "oneshot":  # one-shot decode GEMM: 0 off, 1 planned shapes, 2 every eligible shape

@@ -22,22 +22,6 @@
 
 namespace dnn {
 
-// Phase timestamps of decode-attention block (0,0), thread 0: only in the
-// bench-only probe build (-DDNN_DEC_PROBE, bench/attn_probe.py).
-#ifdef DNN_DEC_PROBE
-__device__ unsigned long long dec_probe_ts[32];
-#define DEC_PROBE(i, dep)                                                             \
-  do {                                                                                \
-    asm volatile("" ::"v"(dep));                                                      \
-    if (threadIdx.x == 0 && (blockIdx.x | blockIdx.y) == 0) {                         \
-      dec_probe_ts[i] = __builtin_amdgcn_s_memrealtime();                             \
-      dec_probe_ts[16 + i] = __builtin_amdgcn_s_memtime();                             \
-    }                                                                                 \
-  } while (0)
-#else
-#define DEC_PROBE(i, dep) do { } while (0)
-#endif
-
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // e4m3 KV cache (KV8) conversions of 8 entries: bf16 -> OCP e4m3 (RNE,
@@ -156,17 +140,14 @@ __device__ __forceinline__ int k_swz(int key, int chunk) {
 // dispatch and the last ones ran alone: GPT-2 B=64 T=512 0.1050 -> 0.0931 ms,
 // T=2048 0.140 -> 0.089, hd 128 T=4096 1.092 -> 0.781 (profiles/r4_flash_lpt_ab.jsonl)
 //
-// PIPE (hd 64, opt-in: DNN_FLASH_PIPE=1): three K/V buffers and
-// two score accumulators, so block j+1's S = K Q^T MFMAs are issued before
-// block j's softmax and P.V — the matrix pipe works through the softmax VALU
-// of the same wave instead of waiting on the S -> max -> exp -> P.V chain
-// (PMC before: MFMA 0.14 busy, profiles/r4_pmc_flash_lpt.md).
-// Measured slower, so off by default: GPT-2 B=64 T=512 0.0950 -> 0.1075 ms,
-// B=8 T=2048 0.0851 -> 0.0986, 4-stage prefill 4.21 -> 4.13 M tok/s
-// (profiles/r5_flash_pipe_ab.jsonl): the second accumulator takes the kernel
-// from 144 to 212 VGPRs and three buffers to 60 KB of LDS, i.e. from 3 to 2
-// workgroups per CU — the lost wave per SIMD overlapped the chain better.
-template <int HD, bool QKV = false, bool KV8 = false, bool DB = false, bool PIPE = false>
+// Two K/V buffers in LDS, one barrier per block: GPT-2 B=64 T=512 0.1075 ->
+// 0.1063 ms against a single buffer, hd 128 T=512 0.251 -> 0.243, T=4096
+// 1.123 -> 1.092 (profiles/r3_flash_double_buffer.jsonl).  A third buffer and
+// a second score accumulator at hd 64 (block j+1's S MFMAs issued before block
+// j's softmax) measured slower, GPT-2 B=64 T=512 0.0950 -> 0.1075 ms
+// (profiles/r5_flash_pipe_ab.jsonl: 212 VGPRs and 60 KB of LDS cost a
+// workgroup per CU), and was removed.
+template <int HD, bool QKV = false, bool KV8 = false>
 __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                             const bf16_t* __restrict__ vc, bf16_t* __restrict__ o, int T,
                                                             int H, int Hkv, int S, const int* __restrict__ pos,
@@ -174,9 +155,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const bf16_t* __rest
                                                             bf16_t* __restrict__ kc_out = nullptr,
                                                             bf16_t* __restrict__ vc_out = nullptr) {
   using SM = FaSmem<HD>;
-  // DB: two K/V buffers, one barrier per block (the block after next is staged
-  // into the other buffer while this one is read)
-  __shared__ __attribute__((aligned(16))) char smem[SM::TOTAL * (PIPE ? 3 : DB ? 2 : 1)];
+  // two K/V buffers: the block after next is staged into the other one while this one is read
+  __shared__ __attribute__((aligned(16))) char smem[SM::TOTAL * 2];
   char* ks = smem;
   char* vs = smem + SM::K_BYTES;
   constexpr int NKS = HD / 16;  // k-steps of the QK^T contraction
@@ -386,74 +366,25 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const bf16_t* __rest
       softmax_pv(kb0, sacc, vs);
     }
   };
-  if constexpr (PIPE) {
-    // blocks j and j+1 staged in buffers j % 3, (j+1) % 3; block j+2 in the
-    // prefetch registers; sc = S of block j.  One barrier per block: past it
-    // every wave is done with block j-1, whose buffer takes block j+2.
-    auto buf = [&](int j) __attribute__((always_inline)) { return smem + (j % 3) * SM::TOTAL; };
-    if (kv_end > 0) {
-      fetch(0, pkA, pvA);
-      ks = buf(0);
-      vs = ks + SM::K_BYTES;
-      stage(pkA, pvA);
-      if (FA_KB < kv_end) {
-        fetch(FA_KB, pkA, pvA);
-        ks = buf(1);
-        vs = ks + SM::K_BYTES;
-        stage(pkA, pvA);
-        if (2 * FA_KB < kv_end) fetch(2 * FA_KB, pkA, pvA);
-      }
-    }
+  if (kv_end > 0) {
+    fetch(0, pkA, pvA);
+    stage(pkA, pvA);
+    if (FA_KB < kv_end) fetch(FA_KB, pkA, pvA);
+  }
+  int buf = 0;
+  for (int kb0 = 0; kb0 < kv_end; kb0 += FA_KB) {
+    // block kb0 is in buffer `buf` and every wave is done with the other one
     __syncthreads();
-    f32x16 sa[2], sb[2];
-    if (kv_end > 0) s_mfma(buf(0), sa);  // block 0 <= wave_qmax always (p0 >= 0)
-    auto iter = [&](int j, f32x16(&sc)[2], f32x16(&sn)[2]) __attribute__((always_inline)) {
-      const int kb0 = j * FA_KB;
-      __syncthreads();
-      if (kb0 + 2 * FA_KB < kv_end) {
-        ks = buf(j + 2);
-        vs = ks + SM::K_BYTES;
-        stage(pkA, pvA);
-        if (kb0 + 3 * FA_KB < kv_end) fetch(kb0 + 3 * FA_KB, pkA, pvA);
-      }
-      if (kb0 + FA_KB < kv_end && kb0 + FA_KB <= wave_qmax) s_mfma(buf(j + 1), sn);
-      if (kb0 <= wave_qmax) softmax_pv(kb0, sc, buf(j) + SM::K_BYTES);
-    };
-    for (int j = 0; j * FA_KB < kv_end; j += 2) {
-      iter(j, sa, sb);
-      if ((j + 1) * FA_KB >= kv_end) break;
-      iter(j + 1, sb, sa);
-    }
-  } else if constexpr (!DB) {
-    if (kv_end > 0) fetch(0, pkA, pvA);
-    for (int kb0 = 0; kb0 < kv_end; kb0 += FA_KB) {
-      stage(pkA, pvA);
-      __syncthreads();
-      if (kb0 + FA_KB < kv_end) fetch(kb0 + FA_KB, pkA, pvA);
-      compute(kb0);
-      __syncthreads();
-    }
-  } else {
-    if (kv_end > 0) {
-      fetch(0, pkA, pvA);
-      stage(pkA, pvA);
-      if (FA_KB < kv_end) fetch(FA_KB, pkA, pvA);
-    }
-    int buf = 0;
-    for (int kb0 = 0; kb0 < kv_end; kb0 += FA_KB) {
-      // block kb0 is in buffer `buf` and every wave is done with the other one
-      __syncthreads();
-      ks = smem + buf * SM::TOTAL;
+    ks = smem + buf * SM::TOTAL;
+    vs = ks + SM::K_BYTES;
+    compute(kb0);
+    if (kb0 + FA_KB < kv_end) {
+      ks = smem + (buf ^ 1) * SM::TOTAL;
       vs = ks + SM::K_BYTES;
-      compute(kb0);
-      if (kb0 + FA_KB < kv_end) {
-        ks = smem + (buf ^ 1) * SM::TOTAL;
-        vs = ks + SM::K_BYTES;
-        stage(pkA, pvA);
-        if (kb0 + 2 * FA_KB < kv_end) fetch(kb0 + 2 * FA_KB, pkA, pvA);
-      }
-      buf ^= 1;
+      stage(pkA, pvA);
+      if (kb0 + 2 * FA_KB < kv_end) fetch(kb0 + 2 * FA_KB, pkA, pvA);
     }
+    buf ^= 1;
   }
   // ---- normalise + store: lane = query, regs = d ----
   if (qrow < T) {
@@ -479,8 +410,6 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const bf16_t* __rest
 // unnormalised partial (o, m, l) to ws; decode_combine merges the splits.
 // ---------------------------------------------------------------------------
 constexpr int DEC_MAXG = 8;
-constexpr int DEC_U = 8;  // key/value rows in flight per thread
-static_assert(DEC_U % 2 == 0, "P.V folds key pairs");
 
 // 8 consecutive head-dim elements [8*sub, 8*sub+8) of one head row, RoPE'd
 // (rotate-half: element i pairs with i +- hd/2) when ROPE, and
@@ -544,11 +473,12 @@ __device__ __forceinline__ void kv8_unpack(const i32x4& w, uint32_t (&p)[8]) {
 // cache; its own scores use the register copy, so no other split touches that
 // row and there is no qkv_split launch.  Otherwise q is head-major (B,H,hd)
 // and lens[b] keys are cached.
-// MF: scores on MFMA.  The LDS-score layout (LPK lanes per key, a 4-step DPP
-// row reduction per key and head) costs ~20 VALU ops per 4 keys and head; with
-// one wave per SIMD (small grids: Llama-3 batch 1 has 8 workgroups) nothing
-// hides that and the score loop, not memory, set the kernel time (~1.2 us per
-// 128 keys, profiles/archive/r2_attn_decode_phase_probe.jsonl).  With MF a wave
+// MF (GQA, G >= 2): scores on MFMA.  The LDS-score layout (LPK lanes per
+// key, a 4-step DPP row reduction per key and head) costs ~20 VALU ops per 4
+// keys and head; with one wave per SIMD (small grids: Llama-3 batch 1 has 8
+// workgroups) nothing hides that and the score loop, not memory, set the
+// kernel time (~1.2 us per 128 keys,
+// profiles/archive/r2_attn_decode_phase_probe.jsonl).  With MF a wave
 // computes S^T for a tile of 16 keys x 16 query-head columns (G used) as
 // HD/32 v_mfma_f32_16x16x32_bf16: lane l feeds key row l&15 (A, straight from
 // the cache) and head l&15 (B = q^T, RoPE'd once); C lands as 4 keys x 1 head
@@ -559,7 +489,7 @@ __device__ __forceinline__ void kv8_unpack(const i32x4& w, uint32_t (&p)[8]) {
 // halve; entries are converted to bf16 in registers (exact) before the same
 // v_dot2 math, and the new key/value row is rounded to e4m3 once — its score
 // uses the rounded copy, so the current step sees what later steps will read.
-template <int HD, int G, int FM, bool NT, bool MF = false, bool KV8 = false, int RU = 0>
+template <int HD, int G, int FM, bool NT, bool KV8 = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ q, int ldq,
                                                           bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
                                                           float* __restrict__ ws, int H, int Hkv, int S,
@@ -568,27 +498,26 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
                                                           int chunk_cap, bf16_t* __restrict__ o_direct) {
   constexpr bool FUSED = FM != 0;  // FM: 0 = q head-major + cached keys, 1 = fused QKV rows, 2 = fused + RoPE
   constexpr bool ROPE = FM == 2;
-  // rows in flight per thread (RU > 0 overrides): KV8 rows are half the bytes,
+  constexpr bool MF = G >= 2;
+  // rows in flight per thread: KV8 rows are half the bytes,
   // so 10 rows keep the same bytes in flight and one batch covers 640 keys at
   // hd 64 (the 512-567-token benchmark contexts take one K and one V round
   // trip, not two).  bf16 MHA with 10 or 12 rows measured neutral (GPT-2 B=64
   // 0.585 / 0.584 / 0.590 ms, profiles/archive/r2_decode_rows_in_flight_bf16_ab.jsonl):
   // that path is bound by the K/V bytes, not by its round trips
-  constexpr int DEC_U = RU > 0 ? RU : (KV8 ? 10 : dnn::DEC_U);
+  constexpr int DEC_U = KV8 ? 10 : 8;
   static_assert(DEC_U % 2 == 0, "P.V folds key pairs");
   constexpr int ELT = KV8 ? 16 : 8;     // head dims per 16-B lane load
   constexpr int LPK = HD / ELT;         // lanes per key row (16 B each)
   constexpr int GPB = 256 / LPK;        // key groups per block
   extern __shared__ __attribute__((aligned(16))) float dsm[];   // [G][chunk_cap] scores, then reduction scratch
   const int bk = blockIdx.x, split = blockIdx.y, NS = gridDim.y;
-  DEC_PROBE(0, 0);
   const int b = bk / Hkv, kvh = bk % Hkv;
   const int p_new = FUSED ? lens[b] : 0;  // FUSED: lens = positions already cached
   const int len = FUSED ? min(p_new + 1, S) : min(lens[b], S);  // never read past the cache capacity
   // splits share the *runtime* length evenly (one captured graph serves every step)
   const int chunk = (len + NS - 1) / NS;
   const int k0 = split * chunk, k1 = min(len, k0 + chunk);
-  DEC_PROBE(1, k1);
   const int tid = threadIdx.x, sub = tid % LPK, grp = tid / LPK;
   float* wsp = ws + ((size_t)bk * NS + split) * G * (HD + 2);
   if (k0 >= k1) {
@@ -659,7 +588,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   }
   float* sc = dsm;  // [G][chunk]
   const int n = k1 - k0;
-  DEC_PROBE(2, nvp[0]);
   if constexpr (MF) {
     static_assert(G <= 16, "MFMA score tile has 16 head columns");
     constexpr int NKC = HD / 32;  // k-steps of 32 dims
@@ -707,7 +635,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (t0 == 0) DEC_PROBE(8, ka[0][0][0]);
 #pragma unroll
       for (int tb = 0; tb < TB; ++tb) {
         const int t = t0 + tb * 4 + wave;
@@ -719,7 +646,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int m = 0; m < NKC; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[tb][m], qB[m], acc, 0, 0, 0);
-        if (t0 == 0 && tb == 0) DEC_PROBE(9, acc[0]);
         if (hj < G) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -771,7 +697,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     }
   }
   }
-  DEC_PROBE(10, 0);
   // first batch of value rows: requested now, in flight across the barrier and
   // the softmax (they depend only on the key range).  Issuing it before the
   // score loop instead measured slower on the e4m3 path (GPT-2 B=64 0.523 ->
@@ -784,7 +709,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     vr0[u] = NT ? __builtin_nontemporal_load(vp) : *vp;
   }
   __syncthreads();
-  DEC_PROBE(3, 0);
   // per-head max and exp (one wave per head, strided)
   __shared__ float mh[DEC_MAXG], lh[DEC_MAXG];
   const int wave = tid >> 6, lane = tid & 63;
@@ -802,7 +726,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     if (lane == 0) { mh[g] = mx; lh[g] = s; }
   }
   __syncthreads();
-  DEC_PROBE(4, 0);
   // P.V: thread owns d chunk `sub` for key group `grp`
   float acc[G][ELT];
 #pragma unroll
@@ -868,7 +791,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
       }
     }
   }
-  DEC_PROBE(5, acc[0][0]);
   __syncthreads();  // scores no longer needed: reuse dsm as [GPB][G][HD] reduction scratch
   float* red = dsm;
 #pragma unroll
@@ -907,7 +829,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     *reinterpret_cast<uint4*>(kb + (size_t)p_new * HD + sub * 8) = wk;
     *reinterpret_cast<uint4*>(vb + (size_t)p_new * HD + sub * 8) = wv;
   }
-  DEC_PROBE(7, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -1367,24 +1288,8 @@ extern "C" int dnn_qkv_split(const void* qkv, void* q, void* kc, void* vc, int B
 template <int HD, bool QKV, bool KV8>
 static void launch_flash(dim3 grid, hipStream_t st, const bf16_t* q, const bf16_t* kc, const bf16_t* vc, bf16_t* o,
                          int T, int H, int Hkv, int S, const int* pos, float sl2, int ldq, bf16_t* kco, bf16_t* vco) {
-  // double-buffered K/V LDS, one barrier per block (default): GPT-2 B=64 T=512 0.1075 -> 0.1063 ms,
-  // hd 128 T=512 0.251 -> 0.243, T=4096 1.123 -> 1.092 (profiles/r3_flash_double_buffer.jsonl);
-  // DNN_FLASH_DB=0 keeps the single buffer (A/B)
-  const char* e = getenv("DNN_FLASH_DB");
-  if constexpr (HD == 64) {  // hd 128: three buffers would leave one workgroup per CU
-    const char* ep = getenv("DNN_FLASH_PIPE");
-    if ((e == nullptr || atoi(e) != 0) && ep != nullptr && atoi(ep) != 0) {
-      hipLaunchKernelGGL((flash_attn_kernel<HD, QKV, KV8, true, true>), grid, dim3(256), 0, st, q, kc, vc, o, T, H,
-                         Hkv, S, pos, sl2, ldq, kco, vco);
-      return;
-    }
-  }
-  if (e == nullptr || atoi(e) != 0)
-    hipLaunchKernelGGL((flash_attn_kernel<HD, QKV, KV8, true>), grid, dim3(256), 0, st, q, kc, vc, o, T, H, Hkv, S,
-                       pos, sl2, ldq, kco, vco);
-  else
-    hipLaunchKernelGGL((flash_attn_kernel<HD, QKV, KV8, false>), grid, dim3(256), 0, st, q, kc, vc, o, T, H, Hkv, S,
-                       pos, sl2, ldq, kco, vco);
+  hipLaunchKernelGGL((flash_attn_kernel<HD, QKV, KV8>), grid, dim3(256), 0, st, q, kc, vc, o, T, H, Hkv, S, pos, sl2,
+                     ldq, kco, vco);
 }
 
 extern "C" int dnn_flash_attn(const void* q, const void* kc, const void* vc, void* o, int B, int T, int H, int Hkv,
@@ -1573,82 +1478,33 @@ static int attn_decode_launch(const void* q, int ldq, void* kc, void* vc, void* 
   dim3 grid(B * Hkv, splits);
   // cache bytes this launch may stream (capacity bound): > 32 MB -> non-temporal
   const bool nt = (double)B * Hkv * S * hd * (kv8 ? 2.0 : 4.0) > 32.0 * 1024 * 1024;
-  // MFMA scores: GQA (G >= 2) by default; DNN_DECODE_MFMA=0/1 forces it off/on (A/B)
-  const char* mf_e = getenv("DNN_DECODE_MFMA");
-  const bool mf = mf_e ? atoi(mf_e) == 1 : G >= 2;
-  const int fm = fused ? (cosT != nullptr ? 2 : 1) : 0;
-  if (kv8) {
-    // DNN_KV8_U=8: 8 rows in flight per thread instead of 10 (A/B)
-    const char* u_e = getenv("DNN_KV8_U");
-    const bool u8 = u_e != nullptr && atoi(u_e) == 8;
-#define DEC8(HDV, NTV, FMV)                                                                                          \
-  if (hd == HDV && nt == NTV && fm == FMV) {                                                                          \
-    if (u8)                                                                                                           \
-      hipLaunchKernelGGL((attn_decode_kernel<HDV, 1, FMV, NTV, false, true, 8>), grid, dim3(256), smem, st,           \
-                         (const bf16_t*)q, ldq, (bf16_t*)kc, (bf16_t*)vc, ws, H, Hkv, S, lens, nullptr, nullptr, sl2,  \
-                         chunk_cap, (bf16_t*)o);                                                                      \
-    else                                                                                                              \
-      hipLaunchKernelGGL((attn_decode_kernel<HDV, 1, FMV, NTV, false, true, 10>), grid, dim3(256), smem, st,          \
-                         (const bf16_t*)q, ldq, (bf16_t*)kc, (bf16_t*)vc, ws, H, Hkv, S, lens, nullptr, nullptr, sl2,  \
-                         chunk_cap, (bf16_t*)o);                                                                      \
-  } else
-    if (G > 1) {  // GQA: MFMA key tiles (hd 128: Llama-3 G = 4, llama3-tiny G = 2)
-#define DEC8G(GV, NTV, FMV)                                                                                           \
-  if (G == GV && nt == NTV && fm == FMV)                                                                              \
-    hipLaunchKernelGGL((attn_decode_kernel<128, GV, FMV, NTV, true, true>), grid, dim3(256), smem, st,                \
-                       (const bf16_t*)q, ldq, (bf16_t*)kc, (bf16_t*)vc, ws, H, Hkv, S, lens, cosT, sinT, sl2,         \
-                       chunk_cap, (bf16_t*)o);                                                                        \
+  const int fm = fused ? (cosT != nullptr ? 2 : 1) : 0;  // cosT is null unless fm == 2
+#define DEC(HDV, GV, FMV, NTV, KV8V)                                                                                  \
+  if (hd == HDV && G == GV && fm == FMV && nt == NTV)                                                                 \
+    hipLaunchKernelGGL((attn_decode_kernel<HDV, GV, FMV, NTV, KV8V>), grid, dim3(256), smem, st, (const bf16_t*)q,    \
+                       ldq, (bf16_t*)kc, (bf16_t*)vc, ws, H, Hkv, S, lens, cosT, sinT, sl2, chunk_cap, (bf16_t*)o);   \
   else
-      DEC8G(4, true, 2) DEC8G(4, false, 2) DEC8G(4, true, 1) DEC8G(4, false, 1) DEC8G(4, true, 0) DEC8G(4, false, 0)
-      DEC8G(2, true, 2) DEC8G(2, false, 2) DEC8G(2, true, 1) DEC8G(2, false, 1) DEC8G(2, true, 0) DEC8G(2, false, 0)
-      { return -2; }
-#undef DEC8G
-    } else
-    DEC8(64, true, 1) DEC8(64, false, 1) DEC8(128, true, 1) DEC8(128, false, 1) DEC8(64, true, 0) DEC8(64, false, 0)
-    DEC8(128, true, 0) DEC8(128, false, 0) { return -2; }
-#undef DEC8
-    if (splits > 1)
-      launch_decode_combine(ws, (bf16_t*)o, B, H, Hkv, hd, splits, st);
-    return (int)hipGetLastError();
+#define DEC_PLAIN(HDV, GV, KV8V)                                                                                      \
+  DEC(HDV, GV, 0, false, KV8V) DEC(HDV, GV, 0, true, KV8V) DEC(HDV, GV, 1, false, KV8V) DEC(HDV, GV, 1, true, KV8V)
+#define DEC_ROPE(HDV, GV, KV8V) DEC(HDV, GV, 2, false, KV8V) DEC(HDV, GV, 2, true, KV8V)
+  if (kv8) {
+    // MHA (DPP scores, no RoPE kernel) at both head dims; GQA (MFMA key tiles) at hd 128: Llama-3 G = 4,
+    // llama3-tiny G = 2
+    DEC_PLAIN(64, 1, true) DEC_PLAIN(128, 1, true)
+    DEC_PLAIN(128, 2, true) DEC_ROPE(128, 2, true) DEC_PLAIN(128, 4, true) DEC_ROPE(128, 4, true) { return -2; }
+  } else {
+    DEC_PLAIN(64, 1, false) DEC_ROPE(64, 1, false) DEC_PLAIN(64, 2, false) DEC_ROPE(64, 2, false)
+    DEC_PLAIN(64, 4, false) DEC_ROPE(64, 4, false) DEC_PLAIN(64, 8, false) DEC_ROPE(64, 8, false)
+    DEC_PLAIN(128, 1, false) DEC_ROPE(128, 1, false) DEC_PLAIN(128, 2, false) DEC_ROPE(128, 2, false)
+    DEC_PLAIN(128, 4, false) DEC_ROPE(128, 4, false) DEC_PLAIN(128, 8, false) DEC_ROPE(128, 8, false) { return -2; }
   }
-#define DEC_FM(HDV, GV, NTV, MFV)                                                                                     \
-  if (fm == 2)                                                                                                        \
-    hipLaunchKernelGGL((attn_decode_kernel<HDV, GV, 2, NTV, MFV>), grid, dim3(256), smem, st, (const bf16_t*)q, ldq,  \
-                       (bf16_t*)kc, (bf16_t*)vc, ws, H, Hkv, S, lens, cosT, sinT, sl2, chunk_cap, (bf16_t*)o);        \
-  else if (fm == 1)                                                                                                   \
-    hipLaunchKernelGGL((attn_decode_kernel<HDV, GV, 1, NTV, MFV>), grid, dim3(256), smem, st, (const bf16_t*)q, ldq,  \
-                       (bf16_t*)kc, (bf16_t*)vc, ws, H, Hkv, S, lens, nullptr, nullptr, sl2, chunk_cap, (bf16_t*)o);  \
-  else                                                                                                                \
-    hipLaunchKernelGGL((attn_decode_kernel<HDV, GV, 0, NTV, MFV>), grid, dim3(256), smem, st, (const bf16_t*)q, ldq,  \
-                       (bf16_t*)kc, (bf16_t*)vc, ws, H, Hkv, S, lens, nullptr, nullptr, sl2, chunk_cap, (bf16_t*)o);
-#define DEC_NT(HDV, GV, NTV)                                                                                          \
-  if (mf) {                                                                                                           \
-    DEC_FM(HDV, GV, NTV, true)                                                                                        \
-  } else {                                                                                                            \
-    DEC_FM(HDV, GV, NTV, false)                                                                                       \
-  }
-#define DEC(HDV, GV)                                                                                                  \
-  if (hd == HDV && G == GV) {                                                                                         \
-    if (nt) {                                                                                                         \
-      DEC_NT(HDV, GV, true)                                                                                           \
-    } else {                                                                                                          \
-      DEC_NT(HDV, GV, false)                                                                                          \
-    }                                                                                                                 \
-  } else
-  DEC(64, 1) DEC(64, 2) DEC(64, 4) DEC(64, 8) DEC(128, 1) DEC(128, 2) DEC(128, 4) DEC(128, 8) { return -2; }
+#undef DEC_ROPE
+#undef DEC_PLAIN
 #undef DEC
-#undef DEC_NT
-#undef DEC_FM
   if (splits > 1)
     launch_decode_combine(ws, (bf16_t*)o, B, H, Hkv, hd, splits, st);
   return (int)hipGetLastError();
 }
-
-#ifdef DNN_DEC_PROBE
-extern "C" int dnn_dec_probe_read(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dec_probe_ts), sizeof(unsigned long long) * 32);
-}
-#endif
 
 extern "C" int dnn_attn_decode(const void* q, const void* kc, const void* vc, void* o, int B, int H, int Hkv, int hd,
                                int S, const int* lens, float scale, int splits, float* ws, hipStream_t st, int kv8) {

@@ -4,7 +4,6 @@ only ever launched with the operand shapes its grid assumes."""
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
@@ -185,8 +184,6 @@ def decode_splits(S: int, B: int, Hkv: int, G: int = 1) -> int:
     split count never drops below ceil(S / floor(40960 / G)) (14 for a 128 K-token
     Llama-3 cache, G = 4), whatever the batch."""
     lds_min = max(1, -(-S // (DEC_LDS_SCORES // max(1, G))))  # ceil(S/splits) * G <= 40960
-    if os.environ.get("DNN_DECODE_SPLITS"):  # A/B override
-        return max(lds_min, int(os.environ["DNN_DECODE_SPLITS"]))
     if B * Hkv >= 512:  # >= 2 workgroups per CU already: the combine pass costs more than it hides
         return lds_min    # (GPT-2 B=64: 0.754 -> 0.703 ms/step, profiles/archive/r1_decode_benches_v6.jsonl)
     want = max(1, -(-1024 // max(1, B * Hkv)))

@@ -1,8 +1,8 @@
 """Every decode-attention route held to the selector fixtures of tests/attn_exact.py
-(MI355X only): the batched split-K kernel (DPP and MFMA scores; head-major q,
-fused QKV rows, fused + RoPE; bf16 and e4m3 caches), the one-pass kernel with
-its RS / KF / KNT switches and forced split counts, both combine kernels, and
-the non-temporal instantiations.
+(MI355X only): the batched split-K kernel (DPP scores at MHA, MFMA scores at
+GQA; head-major q, fused QKV rows, fused + RoPE; bf16 and e4m3 caches), the
+one-pass kernel with its RS / KF / KNT switches and forced split counts, both
+combine kernels, and the non-temporal instantiations.
 
 Each (sequence, head) selects a hand-placed set of 1, 2, 4, 8 or 16 keys: key
 0, key len - 1 (the new key of a fused step), both sides of every split
@@ -21,8 +21,8 @@ new row may change, to exactly the expected bits.
 
 Rows in flight per batch (``GPB * DEC_U`` of attn_decode_kernel): bf16 256 keys
 at hd 64 and 128 at hd 128 (DPP scores), 256 (MFMA scores: 4 waves x 4 tiles);
-e4m3 640 / 512 (DNN_KV8_U=8) at hd 64 and 320 / 256 at hd 128.  The one-pass
-kernel holds a whole split of up to 640 keys.
+e4m3 640 at hd 64 and 320 at hd 128.  The one-pass kernel holds a whole split
+of up to 640 keys.
 
 Found by this file: every fused route (batched and one-pass, bf16 and e4m3)
 loads the value rows of a batch past the context from the clamped row len - 1,
@@ -75,10 +75,8 @@ def _run(fx, kv8=False, ws_splits=None, who=""):
     return ws, out
 
 
-def _batched(monkeypatch, mfma):
+def _batched(monkeypatch):
     monkeypatch.setenv("DNN_DECODE_1P", "0")
-    monkeypatch.setenv("DNN_DECODE_MFMA", mfma)
-    monkeypatch.delenv("DNN_KV8_U", raising=False)
 
 
 def _lens(S, splits, batches, fused):
@@ -88,7 +86,7 @@ def _lens(S, splits, batches, fused):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the batched kernel, bf16 cache: every DEC(hd, G) line x splits x FM x score path
+# the batched kernel, bf16 cache: every (hd, G) of the launch table x splits x FM
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("splits", SPLITS)
 @pytest.mark.parametrize("hd,G", [(64, 1), (64, 2), (64, 4), (64, 8), (128, 1), (128, 2), (128, 4), (128, 8)])
@@ -98,30 +96,26 @@ def test_batched_bf16(hd, G, splits, monkeypatch):
     for fused, rope in FMS:
         lens = _lens(S, splits, batches, fused)
         fx = ax.decode(len(lens), G * Hkv, Hkv, hd, S, lens, splits, fused, rope, edges=(16,) + batches)
-        for mfma in ("0", "1"):
-            _batched(monkeypatch, mfma)
-            ws, _ = _run(fx, who=f"FM={int(fused) + int(rope)} MFMA={mfma}")
-            if splits > 1:
-                assert not torch.isnan(ws).any(), "a split slot nobody wrote"
+        _batched(monkeypatch)
+        ws, _ = _run(fx, who=f"FM={int(fused) + int(rope)}")
+        if splits > 1:
+            assert not torch.isnan(ws).any(), "a split slot nobody wrote"
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the batched kernel, e4m3 cache: every DEC8 / DEC8G line
+# the batched kernel, e4m3 cache: every line of the e4m3 launch table
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("splits", SPLITS)
 @pytest.mark.parametrize("hd", [64, 128])
 def test_batched_e4m3_mha(hd, splits, monkeypatch):
-    """MHA at 10 (default) and 8 (DNN_KV8_U=8) rows in flight; FM 0 and 1 (the e4m3 MHA kernel has no RoPE)."""
+    """MHA (10 rows in flight); FM 0 and 1 (the e4m3 MHA kernel has no RoPE)."""
     S, Hkv = (700, 2) if hd == 64 else (400, 2)
     batches = (512, 640) if hd == 64 else (256, 320)
     for fused in (False, True):
         lens = _lens(S, splits, batches, fused)
         fx = ax.decode(len(lens), Hkv, Hkv, hd, S, lens, splits, fused, False, edges=(16,) + batches)
-        for u in (None, "8"):
-            _batched(monkeypatch, "0")
-            if u:
-                monkeypatch.setenv("DNN_KV8_U", u)
-            _run(fx, kv8=True, who=f"FM={int(fused)} U={u}")
+        _batched(monkeypatch)
+        _run(fx, kv8=True, who=f"FM={int(fused)}")
 
 
 @pytest.mark.parametrize("splits", SPLITS)
@@ -133,7 +127,7 @@ def test_batched_e4m3_gqa(G, splits, monkeypatch):
     for fused, rope in FMS:
         lens = _lens(S, splits, (256,), fused)
         fx = ax.decode(len(lens), G * Hkv, Hkv, hd, S, lens, splits, fused, rope, edges=(16, 256))
-        _batched(monkeypatch, "1")
+        _batched(monkeypatch)
         _run(fx, kv8=True, who=f"FM={int(fused) + int(rope)}")
 
 
@@ -212,13 +206,14 @@ def test_one_pass_without_workspace_falls_back(monkeypatch):
 # non-temporal instantiations: the smallest capacity past the 32 MB rule at B * Hkv = 16
 # ---------------------------------------------------------------------------------------------------------------
 def test_non_temporal_batched_bf16(monkeypatch):
-    S, B, Hkv, G, hd, splits = 4097, 2, 8, 4, 128, 3  # 16 * 4097 * 128 * 4 B > 32 MiB
-    for fused, rope in ((False, False), (True, True)):
-        lens = (S - 1, 4000) if fused else (S, 4001)
-        fx = ax.decode(B, G * Hkv, Hkv, hd, S, lens, splits, fused, rope, edges=(16, 256))
-        for mfma in ("0", "1"):
-            _batched(monkeypatch, mfma)
-            _run(fx, who=f"NT fused={fused} MFMA={mfma}")
+    """G = 4 (MFMA scores) and G = 1 (DPP scores) at the same cache size, head-major and fused."""
+    S, B, Hkv, hd, splits = 4097, 2, 8, 128, 3  # 16 * 4097 * 128 * 4 B > 32 MiB
+    for G in (4, 1):
+        for fused, rope in ((False, False), (True, True)):
+            lens = (S - 1, 4000) if fused else (S, 4001)
+            fx = ax.decode(B, G * Hkv, Hkv, hd, S, lens, splits, fused, rope, edges=(16, 256))
+            _batched(monkeypatch)
+            _run(fx, who=f"NT G={G} fused={fused}")
 
 
 @pytest.mark.parametrize("G", [1, 2])
@@ -226,7 +221,7 @@ def test_non_temporal_batched_e4m3(G, monkeypatch):
     S, B, Hkv, hd, splits = 8193, 2, 8, 128, 5  # 16 * 8193 * 128 * 2 B > 32 MiB
     lens = (S - 1, 8000)
     fx = ax.decode(B, G * Hkv, Hkv, hd, S, lens, splits, True, G > 1, edges=(16, 256, 320))
-    _batched(monkeypatch, "1" if G > 1 else "0")
+    _batched(monkeypatch)
     _run(fx, kv8=True, who="NT e4m3")
 
 
@@ -251,17 +246,18 @@ def test_repeated_launches_are_bit_identical(family, monkeypatch):
     kv8 = family.startswith("e4m3")
     ws_splits = None
     if family in ("batched_dpp", "batched_mfma"):
+        H = 16 if family == "batched_mfma" else 2  # G = 8: MFMA scores; G = 1: DPP scores
         lens = _lens(300, 9, (128, 256), True)
-        fx = ax.decode(len(lens), 16, 2, 128, 300, lens, 9, True, True, edges=(16, 128, 256))
-        _batched(monkeypatch, "1" if family == "batched_mfma" else "0")
+        fx = ax.decode(len(lens), H, 2, 128, 300, lens, 9, True, True, edges=(16, 128, 256))
+        _batched(monkeypatch)
     elif family == "e4m3_mha":
         lens = _lens(700, 9, (512, 640), True)
         fx = ax.decode(len(lens), 2, 2, 64, 700, lens, 9, True, False, edges=(16, 512, 640))
-        _batched(monkeypatch, "0")
+        _batched(monkeypatch)
     elif family == "e4m3_gqa":
         lens = _lens(300, 9, (256,), True)
         fx = ax.decode(len(lens), 8, 2, 128, 300, lens, 9, True, True, edges=(16, 256))
-        _batched(monkeypatch, "1")
+        _batched(monkeypatch)
     else:
         hd, G, rs = (128, 4, None) if family == "one_pass_mfma" else (64, 1, 1)
         lens = _1p_lens(1300, True)

@@ -2,8 +2,8 @@
 tests/attn_exact.py (MI355X only).
 
 Every softmax weight of these fixtures is exactly 0 or 1/n, so the fp64
-attention rounded once to bf16 is the expected output of every route, block
-order and buffering scheme: the comparison is ``torch.equal`` and a difference
+attention rounded once to bf16 is the expected output of every route and block
+order: the comparison is ``torch.equal`` and a difference
 names the query.  One key too many or too few (a causal mask off by one, a
 tile tail taken from a clamped row, a cache row past the length) changes the
 selected set of some query: in every fixture a share of the queries select
@@ -14,9 +14,8 @@ selected score; V: NaN), caches and outputs sit between NaN sentinel slabs, and
 caches are compared before and after as integers: only the chunk's rows may
 change, to exactly the chunk's rows.
 
-Routes: ``qkv_split`` + ``flash_attn`` and ``flash_attn_qkv``, each with the
-single-buffered (DNN_FLASH_DB=0), double-buffered (default) and, at hd 64,
-pipelined (DNN_FLASH_PIPE=1) kernel, on the bf16 and the e4m3 cache.  In the
+Routes: ``qkv_split`` + ``flash_attn`` and ``flash_attn_qkv``, on the bf16 and
+the e4m3 cache, at both head dims.  In the
 case with S = pos + T - 1 the overflow row is dropped and the clipped query is
 excluded, as in test_flash_attn_qkv_matches_split.
 
@@ -36,10 +35,6 @@ DEV = "cuda"
 
 CASES = [(c, h, hd) for c in ax.PREFILL_CASES for h in ax.PREFILL_HEADS for hd in (64, 128)]
 IDS = [f"{ax.prefill_id(c)}-H{h[0]}kv{h[1]}-hd{hd}" for c, h, hd in CASES]
-
-
-def _modes(hd):
-    return [("0", "0"), ("1", "0")] + ([("1", "1")] if hd == 64 else [])
 
 
 def _fx(case, heads, hd):
@@ -88,33 +83,30 @@ def _assert_q(fx, qb, q, who):
 
 
 @pytest.mark.parametrize("case,heads,hd", CASES, ids=IDS)
-def test_flash_routes_select_exactly(case, heads, hd, monkeypatch):
+def test_flash_routes_select_exactly(case, heads, hd):
     from distributed_neural_networks_amd.ops import transformer_ops as T
     fx = _fx(case, heads, hd)
     B, Tn, H, Hkv = fx.B, fx.T, fx.H, fx.Hkv
     qkv = fx.qkv.to(DEV)
     pos = torch.tensor(fx.pos, device=DEV, dtype=torch.int32)
     for kv8 in (False, True):
-        for db, pipe in _modes(hd):
-            monkeypatch.setenv("DNN_FLASH_DB", db)
-            monkeypatch.setenv("DNN_FLASH_PIPE", pipe)
-            who = f"{'e4m3' if kv8 else 'bf16'} DB={db} PIPE={pipe}"
-            # qkv_split, then flash_attn over the cache
-            kb, kc, vb, vc = _caches(fx, kv8)
-            qb, q = _split_q(fx, qkv, kc, vc, pos)
-            ob, out = ax.nan_like((B * Tn, H * hd), torch.bfloat16, DEV)
-            T.flash_attn(q, kc, vc, out, B, Tn, H, Hkv, hd, pos)
-            torch.cuda.synchronize()
-            _assert_q(fx, qb, q, "qkv_split " + who)
-            _assert_cache(fx, kv8, kb, kc, vb, vc, True, "qkv_split + flash_attn " + who)
-            _assert_out(fx, ob, out, "flash_attn " + who)
-            # flash_attn_qkv: the chunk's keys from the qkv rows, the cache written on the way
-            kb, kc, vb, vc = _caches(fx, kv8)
-            ob, out = ax.nan_like((B * Tn, H * hd), torch.bfloat16, DEV)
-            T.flash_attn_qkv(qkv, kc, vc, out, B, Tn, H, Hkv, hd, pos)
-            torch.cuda.synchronize()
-            _assert_cache(fx, kv8, kb, kc, vb, vc, True, "flash_attn_qkv " + who)
-            _assert_out(fx, ob, out, "flash_attn_qkv " + who)
+        who = "e4m3" if kv8 else "bf16"
+        # qkv_split, then flash_attn over the cache
+        kb, kc, vb, vc = _caches(fx, kv8)
+        qb, q = _split_q(fx, qkv, kc, vc, pos)
+        ob, out = ax.nan_like((B * Tn, H * hd), torch.bfloat16, DEV)
+        T.flash_attn(q, kc, vc, out, B, Tn, H, Hkv, hd, pos)
+        torch.cuda.synchronize()
+        _assert_q(fx, qb, q, "qkv_split " + who)
+        _assert_cache(fx, kv8, kb, kc, vb, vc, True, "qkv_split + flash_attn " + who)
+        _assert_out(fx, ob, out, "flash_attn " + who)
+        # flash_attn_qkv: the chunk's keys from the qkv rows, the cache written on the way
+        kb, kc, vb, vc = _caches(fx, kv8)
+        ob, out = ax.nan_like((B * Tn, H * hd), torch.bfloat16, DEV)
+        T.flash_attn_qkv(qkv, kc, vc, out, B, Tn, H, Hkv, hd, pos)
+        torch.cuda.synchronize()
+        _assert_cache(fx, kv8, kb, kc, vb, vc, True, "flash_attn_qkv " + who)
+        _assert_out(fx, ob, out, "flash_attn_qkv " + who)
 
 
 @pytest.mark.parametrize("kv8", [False, True], ids=["bf16", "e4m3"])

@@ -67,7 +67,8 @@ def _attn_ref(q, k, v, pos0):
 
 
 @pytest.mark.parametrize("B,Tn,H,Hkv,hd,pos0", [(2, 64, 4, 4, 64, 0), (1, 200, 12, 12, 64, 0), (2, 77, 8, 2, 128, 0),
-                                                 (1, 33, 4, 1, 128, 40), (3, 130, 2, 2, 64, 17), (1, 1024, 2, 2, 128, 0)])
+                                                 (1, 33, 4, 1, 128, 40), (3, 130, 2, 2, 64, 17), (1, 1024, 2, 2, 128, 0),
+                                                 (3, 200, 12, 12, 64, 0), (2, 517, 4, 2, 64, 0)])
 def test_qkv_split_flash(B, Tn, H, Hkv, hd, pos0):
     from distributed_neural_networks_amd.ops import transformer_ops as T
     torch.manual_seed(1)
@@ -90,7 +91,8 @@ def test_qkv_split_flash(B, Tn, H, Hkv, hd, pos0):
 
 
 @pytest.mark.parametrize("B,Tn,H,Hkv,hd,pos0", [(2, 64, 4, 4, 64, 0), (1, 200, 12, 12, 64, 0), (2, 77, 8, 2, 128, 0),
-                                                 (1, 33, 4, 1, 128, 40), (3, 130, 2, 2, 64, 17), (2, 300, 4, 2, 64, 250)])
+                                                 (1, 33, 4, 1, 128, 40), (3, 130, 2, 2, 64, 17), (2, 300, 4, 2, 64, 250),
+                                                 (3, 200, 12, 12, 64, 0), (2, 517, 4, 2, 64, 0)])
 def test_flash_attn_qkv_matches_split(B, Tn, H, Hkv, hd, pos0):
     """Prefill straight from the c_attn output (no qkv_split): identical output
     and identical cache contents to qkv_split + flash_attn, including chunked
@@ -142,40 +144,6 @@ def test_row_stats_rows_per_wave(M, N, rms, monkeypatch):
     assert torch.allclose(outs[1][:, 1], -mean * rstd, rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("B,Tn,H,Hkv,hd,pos0", [(2, 64, 4, 4, 64, 0), (3, 200, 12, 12, 64, 0), (2, 77, 8, 2, 128, 0),
-                                                 (1, 33, 4, 1, 128, 40), (3, 130, 2, 2, 64, 17), (2, 517, 4, 2, 64, 0)])
-def test_flash_double_buffer_bit_identical(B, Tn, H, Hkv, hd, pos0, monkeypatch):
-    """Double-buffered K/V LDS with one barrier per block (DNN_FLASH_DB=1) and
-    the hd-64 software-pipelined variant (three buffers, next block's scores
-    issued before this block's softmax: DNN_FLASH_PIPE=1, opt-in) are the
-    same arithmetic as the single buffer: outputs and written caches
-    bit-identical, head-major and QKV mode, chunked prefill and GQA."""
-    from distributed_neural_networks_amd.ops import transformer_ops as T
-    torch.manual_seed(4)
-    S = pos0 + Tn + 8
-    kc0 = torch.randn(B, Hkv, S, hd, device=DEV).bfloat16()
-    vc0 = torch.randn(B, Hkv, S, hd, device=DEV).bfloat16()
-    qkv = torch.randn(B * Tn, (H + 2 * Hkv) * hd, device=DEV).bfloat16()
-    pos = torch.full((B,), pos0, device=DEV, dtype=torch.int32)
-    q = torch.empty(B * H * Tn * hd, device=DEV, dtype=torch.bfloat16)
-    outs = []
-    for db, pipe in (("0", "0"), ("1", "0"), ("1", "1")):
-        monkeypatch.setenv("DNN_FLASH_DB", db)
-        monkeypatch.setenv("DNN_FLASH_PIPE", pipe)
-        kc, vc = kc0.clone(), vc0.clone()
-        T.qkv_split(qkv, q, kc, vc, B, Tn, H, Hkv, hd, pos)
-        o1 = torch.empty(B * Tn, H * hd, device=DEV, dtype=torch.bfloat16)
-        T.flash_attn(q, kc, vc, o1, B, Tn, H, Hkv, hd, pos)
-        kc2, vc2 = kc0.clone(), vc0.clone()
-        o2 = torch.empty_like(o1)
-        T.flash_attn_qkv(qkv, kc2, vc2, o2, B, Tn, H, Hkv, hd, pos)
-        outs.append((o1, o2, kc2, vc2))
-    torch.cuda.synchronize()
-    for other in outs[1:]:
-        for a, b in zip(outs[0], other):
-            assert torch.equal(a, b)
-
-
 def test_flash_attn_spike_rescale():
     """Force the online-softmax rescale: one huge key score late in the sequence (guide §5.4 rule 26)."""
     from distributed_neural_networks_amd.ops import transformer_ops as T
@@ -193,8 +161,7 @@ def test_flash_attn_spike_rescale():
 
 
 def _decode_path(monkeypatch, path):
-    """'0' / '1': the batched kernel with DPP / MFMA scores; '1p': the one-pass
-    kernel, forced onto grids of any size."""
+    """'batched': the batched kernel everywhere; '1p': the one-pass kernel, forced onto grids of any size."""
     if path in ("1p", "1p_rs", "1p_kf"):
         monkeypatch.setenv("DNN_DECODE_1P", "2")
         monkeypatch.setenv("DNN_DECODE_1P_RS", "1" if path == "1p_rs" else "0")
@@ -205,20 +172,19 @@ def _decode_path(monkeypatch, path):
             monkeypatch.delenv(k, raising=False)
     else:
         monkeypatch.setenv("DNN_DECODE_1P", "0")
-        monkeypatch.setenv("DNN_DECODE_MFMA", path)
 
 
 @pytest.mark.parametrize("B,H,Hkv,hd,S,lens", [(2, 12, 12, 64, 1024, [1, 700]), (3, 32, 8, 128, 2048, [5, 1000, 2048]),
                                                (1, 4, 2, 128, 300, [299]), (4, 25, 25, 64, 512, [17, 64, 65, 512]),
                                                (1, 32, 8, 128, 131072, [120001]),   # long context: LDS-bound splits
                                                (2, 12, 12, 64, 65536, [65536, 9000])])
-@pytest.mark.parametrize("mfma", ["0", "1", "1p", "1p_rs", "1p_kf", "1p_default"])
-def test_attn_decode(B, H, Hkv, hd, S, lens, mfma, monkeypatch):
-    """Both score paths of the batched decode kernel (DPP row reductions and
-    MFMA key tiles, forced by DNN_DECODE_MFMA) and the one-pass kernel (forced
-    by DNN_DECODE_1P=2 on these small grids; long caches fall back)."""
+@pytest.mark.parametrize("path", ["batched", "1p", "1p_rs", "1p_kf", "1p_default"])
+def test_attn_decode(B, H, Hkv, hd, S, lens, path, monkeypatch):
+    """The batched decode kernel (DPP row reductions at MHA, MFMA key tiles at
+    GQA) and the one-pass kernel (forced by DNN_DECODE_1P=2 on these small
+    grids; long caches fall back)."""
     from distributed_neural_networks_amd.ops import transformer_ops as T
-    _decode_path(monkeypatch, mfma)
+    _decode_path(monkeypatch, path)
     torch.manual_seed(2)
     q = torch.randn(B, H, hd, device=DEV).bfloat16()
     kc = torch.randn(B, Hkv, S, hd, device=DEV).bfloat16()
@@ -717,14 +683,14 @@ def test_linear_norm_strided_rows():
     (1, 32, 8, 128, 200, [150], True, 1), (3, 12, 12, 64, 300, [0, 17, 299], False, 2),
     (2, 8, 2, 128, 1024, [700, 1023], True, 4), (2, 4, 4, 64, 64, [63, 64], False, 1),
     (1, 32, 8, 128, 600, [140], True, 1), (1, 32, 8, 128, 600, [599], True, 3)])
-@pytest.mark.parametrize("mfma", ["0", "1", "1p", "1p_rs", "1p_kf", "1p_default"])
-def test_attn_decode_qkv_fused(B, H, Hkv, hd, S, pos, rope, splits, mfma, monkeypatch):
+@pytest.mark.parametrize("path", ["batched", "1p", "1p_rs", "1p_kf", "1p_default"])
+def test_attn_decode_qkv_fused(B, H, Hkv, hd, S, pos, rope, splits, path, monkeypatch):
     """Fused decode step (split + RoPE + cache write + attention) == qkv_split
     then attn_decode, and the cache row it wrote matches; pos >= S (overflow)
     writes nothing and attends to the S cached keys."""
     from distributed_neural_networks_amd.models.llama3 import LLAMA_CONFIGS, rope_tables
     from distributed_neural_networks_amd.ops import transformer_ops as T
-    _decode_path(monkeypatch, mfma)
+    _decode_path(monkeypatch, path)
     torch.manual_seed(9)
     kc = torch.randn(B, Hkv, S, hd, device=DEV).bfloat16()
     vc = torch.randn(B, Hkv, S, hd, device=DEV).bfloat16()

@@ -9,7 +9,6 @@
 #   flash_check      flash / decode attention tests, flash-vs-SDPA bench, GPT-2 prefill
 #   gemm_epi         GEMM epilogue cost on the GPT-2 prefill shapes: bias / +GELU / +residual (separate, in place)
 #   kv8              fp8 (e4m3) KV cache: numerics, then GPT-2 / GPT-2 XL decode, bf16 vs fp8 cache
-#   kv8_ab           fp8-KV decode attention rows in flight per thread: 10 vs 8 (in-process A/B).
 #   kv8g             fp8 KV for GQA / RoPE (Llama-3): tests, then Llama-3 8B B=32 decode bf16 vs fp8 KV.
 #   prof_argmax      Llama-3 8B fp8 B=1 decode kernel gaps with the split argmax
 #   prof_llama_b32   Llama-3 8B bf16 B=32 decode kernel table + gaps, M=32 projection sweep
@@ -88,19 +87,6 @@ case_kv8() {
   "; return $rc
 }
 
-case_kv8_ab() {
-  # fp8-KV decode attention rows in flight per thread: 10 vs 8 (in-process A/B).
-  timeout -k 10 200 python -u -m pytest tests/test_kv8_gpu.py -m gpu -x -q --timeout 120 --timeout-method thread \
-    > gpurun_out/kv8u_tests.log 2>&1
-  rc=$?; tail -2 gpurun_out/kv8u_tests.log; [ $rc -eq 0 ] || return $rc
-  out=gpurun_out/kv8u_ab.jsonl; : > $out
-  ab() { timeout -k 10 300 python -u bench/probes/decode_ab.py --switch kv8_u --values 8,10 "$@" >> $out 2> gpurun_out/kv8u_ab.err; }
-  ab --steps 32 --warmup 4 --prefill_iters 1 --kv fp8 &&
-  ab --batch 256 --steps 32 --warmup 4 --prefill_iters 1 --kv fp8 &&
-  ab --model gpt2-xl --stages 8 --batch 64 --prompt 512 --dtype fp8 --kv fp8 --steps 16 --warmup 2 --prefill_iters 1
-  rc=$?; cat $out; return $rc
-}
-
 case_kv8g() {
   # fp8 KV for GQA / RoPE (Llama-3): tests, then Llama-3 8B B=32 decode bf16 vs fp8 KV.
   timeout -k 10 300 python -u -m pytest tests/test_kv8_gpu.py tests/test_transformer_gpu.py tests/test_pipeline_gpu.py -m gpu -x -q \
@@ -168,6 +154,6 @@ case_prof_kv8() {
 
 c=${1:-}
 if ! declare -F "case_$c" > /dev/null; then
-  echo "usage: $0 <case>; cases: argmax_ab decode_ab decode_check flash_check gemm_epi kv8 kv8_ab kv8g prof_argmax prof_llama_b32 scatter3 prof_kv8 tail_check"; exit 2
+  echo "usage: $0 <case>; cases: argmax_ab decode_ab decode_check flash_check gemm_epi kv8 kv8g prof_argmax prof_llama_b32 scatter3 prof_kv8 tail_check"; exit 2
 fi
 "case_$c"

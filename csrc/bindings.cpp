@@ -250,6 +250,15 @@ PYBIND11_MODULE(_dnn_hip, m) {
                                CIP(prev), rep, freq, pres, ST(st));
   }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("cnt"), py::arg("cnt_ld"), py::arg("prev"),
      py::arg("rep"), py::arg("freq"), py::arg("pres"), py::arg("st"));
+  m.def("logprobs_ws_row_words", [](int N, int n) { return dnn_logprobs_ws_row_words(N, n); }, py::arg("N"),
+        py::arg("n"));
+  m.def("logprobs_rows", [](u64 x, int ld, int M, int N, u64 tok, u64 pos, int pos_off, int n, u64 lp_hist,
+                            u64 top_id_hist, u64 top_lp_hist, int hist_ld, int top_ld, u64 ws, int ws_rows, int ws_ld, u64 st) {
+    return dnn_logprobs_rows(CP(x), ld, M, N, CIP(tok), CIP(pos), pos_off, n, FP(lp_hist), IP(top_id_hist),
+                             FP(top_lp_hist), hist_ld, top_ld, P(ws), ws_rows, ws_ld, ST(st));
+  }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("tok"), py::arg("pos"), py::arg("pos_off"),
+     py::arg("n"), py::arg("lp_hist"), py::arg("top_id_hist"), py::arg("top_lp_hist"), py::arg("hist_ld"),
+     py::arg("top_ld"), py::arg("ws"), py::arg("ws_rows"), py::arg("ws_ld"), py::arg("st"));
   m.def("quant_fp8_rows", [](u64 x, int ldx, u64 q, u64 scale, int M, int K, int kpad, u64 st, int split) {
     return dnn_quant_fp8_rows(CP(x), ldx, P(q), FP(scale), M, K, kpad, ST(st), split);
   }, py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("scale"), py::arg("M"), py::arg("K"), py::arg("kpad"),

@@ -142,6 +142,18 @@ int dnn_argmax_rows(const void* x, int ld, int M, int N, int* out, int f32in, hi
 // not 16-byte aligned, rep not > 0, freq / pres not finite
 int dnn_logit_penalties(void* x, int ld, int M, int N, unsigned short* cnt, int cnt_ld, const int* prev, float rep,
                         float freq, float pres, hipStream_t st);
+// log-probability of tok[row] and the n <= 20 most likely entries (value descending, index ascending) of
+// every row of bf16 logits (logprobs.hip), written at position p = pos[row] + pos_off (pos null: pos_off) of
+// the histories lp_hist[row, p], top_id_hist / top_lp_hist[row, p, 0..n) (top_ld entries per position);
+// p outside [0, hist_ld) writes nothing.  ws: ws_rows >= M blocks of ws_ld >= dnn_logprobs_ws_row_words(N, n)
+// 32-bit words (a multiple of 32), zero before the first call; the kernel leaves each block's counter, its
+// first 32 words, zero and writes nothing else there, so calls of any M, N, n may share a workspace.
+// -1: null x / tok / lp_hist / ws, ld not a multiple of 8 or below N, x not 16-byte aligned, n outside
+// [0, min(20, N)], top histories missing or top_ld < n, ws too small; -2: M > 65535 or N > 102 * 2048
+int dnn_logprobs_ws_row_words(int N, int n);
+int dnn_logprobs_rows(const void* x, int ld, int M, int N, const int* tok, const int* pos, int pos_off, int n,
+                      float* lp_hist, int* top_id_hist, float* top_lp_hist, int hist_ld, int top_ld, void* ws,
+                      int ws_rows, int ws_ld, hipStream_t st);
 int dnn_quant_fp8_rows(const void* x, int ldx, void* q, float* scale, int M, int K, int kpad, hipStream_t st,
                        int split = 0);
 int dnn_gemm_fp8(const void* A, const float* sa, const void* W, const float* sw, void* C, int ldc, const float* bias,

@@ -12,7 +12,8 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
 * Additive optional fields (absent in the reference file, so it still loads):
   top level ``model``, ``dtype``, ``transport``, ``micro_batch_size``,
   ``num_microbatches``, ``seq_len``, ``decode_steps``, ``prompt_len``, ``temperature``, ``top_k``,
-  ``top_p``, ``min_p``, ``seed``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
+  ``top_p``, ``min_p``, ``seed``, ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``,
+  ``logprobs``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
   ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``input_dtype``, ``input_mean``,
   ``input_std`` (CIFAR: stage 0 takes uint8 images and normalises them by table); per node
   ``layers: [start, end]`` (inclusive, as in
@@ -54,6 +55,11 @@ class NodeSpec:
         return int(self.address.rsplit(":", 1)[-1])
 
 
+# most alternatives per token that 'logprobs' records: OpenAI's top_logprobs limit; the candidate slots of
+# csrc/kernels/logprobs.hip (LP_MAX_N) are sized by it
+LOGPROBS_MAX_N = 20
+
+
 @dataclass
 class PipelineConfig:
     """The whole topology: every stage, in stage order."""
@@ -82,6 +88,7 @@ class PipelineConfig:
     repetition_penalty: float = 1.0           # > 0; seen (prompt or generated) tokens: logit / r if > 0 else * r (1 = off)
     presence_penalty: float = 0.0             # subtracted once from the logit of every generated token (0 = off)
     frequency_penalty: float = 0.0            # subtracted per time the token was generated (0 = off)
+    logprobs: int = 0                         # 1..20: record each token's log-probability and the top-n (0 = off)
     rpc_timeout_s: Optional[float] = None     # per-hop SendTensor deadline (reference: none)
     health_timeout_s: float = 120.0           # readiness barrier before stage 0 sends
     comm_timeout_s: float = 300.0             # process-group (RCCL/gloo) op timeout
@@ -237,6 +244,11 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v):
             raise ConfigError(f"ERROR: '{key}' must be a finite number, got {v!r}")
         pens[key] = float(v)
+    nlp = cfg.get("logprobs", 0)
+    if not isinstance(nlp, int) or isinstance(nlp, bool) or not 0 <= nlp <= LOGPROBS_MAX_N:
+        raise ConfigError(f"ERROR: 'logprobs' must be an integer in [0, {LOGPROBS_MAX_N}], got {nlp!r}")
+    if model == "cifar10" and nlp != 0:
+        raise ConfigError(f"ERROR: 'logprobs' {nlp!r} exists for the generating models only, got model '{model}'")
     if model == "cifar10":
         for key, v, neutral in (("repetition_penalty", rp, 1), ("presence_penalty", pens["presence_penalty"], 0),
                                 ("frequency_penalty", pens["frequency_penalty"], 0)):
@@ -271,7 +283,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         prefill_chunk=int(cfg.get("prefill_chunk", 0)),
         temperature=float(cfg.get("temperature", 0.0)), top_k=int(cfg.get("top_k", 0)), seed=int(cfg.get("seed", 0)),
         top_p=float(tp), min_p=float(mp), repetition_penalty=float(rp), presence_penalty=pens["presence_penalty"],
-        frequency_penalty=pens["frequency_penalty"],
+        frequency_penalty=pens["frequency_penalty"], logprobs=nlp,
         rpc_timeout_s=cfg.get("rpc_timeout_s"), health_timeout_s=float(cfg.get("health_timeout_s", 120.0)),
         comm_timeout_s=float(cfg.get("comm_timeout_s", 300.0)),
         heartbeat_timeout_s=float(cfg.get("heartbeat_timeout_s", 15.0)),

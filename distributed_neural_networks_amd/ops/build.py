@@ -44,6 +44,9 @@ PER_FILE_FLAGS = {"cifar_fused.hip": ["-ffast-math"],
                   # the penalty arithmetic is bitwise its torch mirror: multiply and subtract stay
                   # two roundings (no FMA)
                   "penalties.hip": ["-ffp-contract=off"] + NO_SLP,
+                  # log-probabilities: (x - max) - log(sum) stays two subtractions, so the exact
+                  # fixtures (tests/test_logprobs_gpu.py) hold bit for bit
+                  "logprobs.hip": ["-ffp-contract=off"] + NO_SLP,
                   "gemm_skinny.hip": NO_SLP,
                   "gemm_bf16.hip": NO_SLP}
 

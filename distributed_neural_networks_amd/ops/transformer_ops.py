@@ -8,6 +8,7 @@ from typing import Optional
 
 import torch
 
+from ..config import LOGPROBS_MAX_N
 from ._lib import check, lib, ptr, stream_ptr
 
 
@@ -353,3 +354,75 @@ def logit_penalties(logits: torch.Tensor, cnt: torch.Tensor, prev: Optional[torc
     check(lib().logit_penalties(x=ptr(logits), ld=ld, M=M, N=n, cnt=ptr(cnt), cnt_ld=cnt_ld, prev=ptr(prev), rep=rep,
                                 freq=freq, pres=pres, st=stream_ptr()), "logit_penalties")
     return logits
+
+
+
+
+def logprobs_workspace(rows: int, n_vocab: int, n: int, device) -> torch.Tensor:
+    """Zeroed workspace of ``logprobs_rows`` for up to ``rows`` rows of up to
+    ``n_vocab`` logits and up to ``n`` alternatives: int32 (rows, words), one
+    block per row: its arrival counter in the first 32 words (which the kernel
+    leaves at zero and never uses for anything else) and the per-chunk partial
+    results of one launch behind them.  A counter's place depends on the tensor
+    alone, so calls on fewer rows, a smaller vocabulary or fewer alternatives
+    may share one workspace; one launch at a time."""
+    words = int(lib().logprobs_ws_row_words(N=int(n_vocab), n=int(n)))
+    if rows <= 0 or words <= 0:
+        raise ValueError(f"logprobs_workspace: unsupported rows {rows}, vocabulary {n_vocab} or n {n}")
+    return torch.zeros((int(rows), words), dtype=torch.int32, device=device)
+
+
+def logprobs_rows(logits: torch.Tensor, tokens: torch.Tensor, n_vocab: int, n: int, chosen: torch.Tensor,
+                  top_ids: Optional[torch.Tensor], top_lps: Optional[torch.Tensor], ws: torch.Tensor,
+                  pos: Optional[torch.Tensor] = None, pos_off: int = 0) -> None:
+    """Log-probabilities of one step (logprobs.hip; ``runtime/sampling.logprobs_ref``
+    is the fp64 mirror).  For every row of bf16 ``logits`` (M, >= n_vocab):
+    ``lse = logsumexp`` over the first ``n_vocab`` entries, and at position
+    ``p = pos[row] + pos_off`` (``pos`` None: ``pos_off``) of the histories
+    ``chosen[row, p] = logits[row, tokens[row]] - lse`` (NaN for a token outside
+    the vocabulary) and, with ``n`` >= 1, ``top_ids[row, p, :n]`` /
+    ``top_lps[row, p, :n]`` = the ``n`` largest entries ordered by (value
+    descending, index ascending).  ``chosen`` fp32 (>= M, L), ``top_ids`` int32
+    and ``top_lps`` fp32 (>= M, L, >= n), all contiguous; a position outside
+    [0, L) writes nothing.  ``pos_off = -1`` serves a step whose fused tail has
+    advanced ``pos`` already.  ``ws``: ``logprobs_workspace``."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("logprobs_rows: bf16 (M, >= n_vocab) logits with contiguous rows expected")
+    M = logits.shape[0]
+    if not 0 < n_vocab <= logits.shape[1]:
+        raise ValueError(f"logprobs_rows: n_vocab = {n_vocab} outside the row width {logits.shape[1]}")
+    n = int(n)
+    if not 0 <= n <= min(LOGPROBS_MAX_N, n_vocab):
+        raise ValueError(f"logprobs_rows: n = {n} outside [0, {min(LOGPROBS_MAX_N, n_vocab)}]")
+    ld = logits.stride(0) if M > 1 else logits.shape[1]
+    if ld % 8 or ld < n_vocab or logits.data_ptr() % 16:
+        raise ValueError("logprobs_rows: rows must start 16-byte aligned (row stride a multiple of 8, >= n_vocab)")
+    if tokens.dtype != torch.int32 or tokens.numel() < M or not tokens.is_contiguous():
+        raise ValueError(f"logprobs_rows: tokens must be contiguous int32 with >= {M} entries")
+    if pos is not None and (pos.dtype != torch.int32 or pos.numel() < M or not pos.is_contiguous()):
+        raise ValueError(f"logprobs_rows: pos must be contiguous int32 with >= {M} entries")
+    if chosen.dtype != torch.float32 or chosen.dim() != 2 or not chosen.is_contiguous() or chosen.shape[0] < M:
+        raise ValueError(f"logprobs_rows: chosen must be contiguous fp32 (>= {M}, L), got {chosen.dtype} "
+                         f"{tuple(chosen.shape)}")
+    L = chosen.shape[1]
+    top_ld = 0
+    if n > 0:
+        if top_ids is None or top_lps is None:
+            raise ValueError("logprobs_rows: n >= 1 needs top_ids and top_lps")
+        for t, dt, name in ((top_ids, torch.int32, "top_ids"), (top_lps, torch.float32, "top_lps")):
+            if (t.dtype != dt or t.dim() != 3 or not t.is_contiguous() or t.shape[0] < M or t.shape[1] != L
+                    or t.shape[2] < n):
+                raise ValueError(f"logprobs_rows: {name} must be contiguous {dt} (>= {M}, {L}, >= {n}), got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+        if top_ids.shape[2] != top_lps.shape[2]:
+            raise ValueError("logprobs_rows: top_ids and top_lps differ in their last dimension")
+        top_ld = top_ids.shape[2]
+    need = int(lib().logprobs_ws_row_words(N=int(n_vocab), n=n))
+    if (ws.dtype != torch.int32 or ws.dim() != 2 or not ws.is_contiguous() or ws.shape[0] < M or ws.shape[1] % 32
+            or need <= 0 or ws.shape[1] < need):
+        raise ValueError(f"logprobs_rows: workspace {ws.dtype} {tuple(ws.shape)}, contiguous int32 (>= {M}, >= {need}) "
+                         f"needed (logprobs_workspace)")
+    check(lib().logprobs_rows(x=ptr(logits), ld=ld, M=M, N=int(n_vocab), tok=ptr(tokens), pos=ptr(pos),
+                              pos_off=int(pos_off), n=n, lp_hist=ptr(chosen), top_id_hist=ptr(top_ids if n else None),
+                              top_lp_hist=ptr(top_lps if n else None), hist_ld=L, top_ld=top_ld, ws=ptr(ws),
+                              ws_rows=ws.shape[0], ws_ld=ws.shape[1], st=stream_ptr()), "logprobs_rows")

@@ -19,6 +19,7 @@ Stage 0 prints the reference's ``***** FINAL PREDICTION (Index): k *****`` line
 from __future__ import annotations
 
 import json
+import math
 import time
 from typing import List, Optional
 
@@ -84,6 +85,30 @@ def _report(nid: str, toks: torch.Tensor, prefill_s: float, decode_s: float, n_s
     log("METRICS " + json.dumps(m))
 
 
+def _report_logprobs(nid: str, ring: DecodeRing) -> None:
+    """One ``LOGPROBS {...}`` JSON line from the rank that holds them (the last
+    stage's; config key ``logprobs``): every sequence's chosen log-probabilities,
+    aligned with the ``generated tokens`` line, and the first sequence's top-n
+    (``DNN_LOGPROBS_ALL=1``: also every sequence's, as ``top_ids`` /
+    ``top_logprobs``).  The numbers are the fp32 values, written so that they
+    read back exactly; -inf and NaN, which JSON lacks, are null."""
+    if ring.lp_chosen is None:
+        return
+    import os
+
+    def fin(t):
+        if isinstance(t, list):
+            return [fin(v) for v in t]
+        return t if math.isfinite(t) else None
+    lp = ring.logprobs()
+    rec = {"node": nid, "n": int(lp["top_ids"].shape[2]), "chosen": fin(lp["chosen"].tolist()),
+           "top_ids_seq0": lp["top_ids"][0].tolist(), "top_logprobs_seq0": fin(lp["top_lps"][0].tolist())}
+    if os.environ.get("DNN_LOGPROBS_ALL") == "1":
+        rec["top_ids"] = lp["top_ids"].tolist()
+        rec["top_logprobs"] = fin(lp["top_lps"].tolist())
+    log("LOGPROBS " + json.dumps(rec))
+
+
 def _timed_generate(ring: DecodeRing, prompts, T: int, steps: int, dev, chunk: int = 0):
     t0 = time.perf_counter()
     ring.prefill(prompts, T, chunk)
@@ -110,6 +135,7 @@ def run_generate_colocated(ctx, args, stages: List, device) -> int:
     prompts = [prompt[m * B:(m + 1) * B] for m in range(M)]
     pf, dec = _timed_generate(ring, prompts, T, steps, device, pipe.prefill_chunk)
     _report(ctx.node_id, ring.tokens(), pf, dec, n_seq, T, steps, M, 1)
+    _report_logprobs(ctx.node_id, ring)
     return 0
 
 
@@ -147,4 +173,5 @@ def run_generate_dist(ctx, args, stage, info, progress=None) -> int:
     if r == 0:
         nid = ctx.node_id + (f" replica {ctx.replica}" if getattr(pipe, "replicas", 1) > 1 else "")
         _report(nid, ring.tokens(), pf, dec, B * M, T, steps, M, S)
+    _report_logprobs(ctx.node_id, ring)  # the last rank's: nothing new travels over the back-edge
     return 0

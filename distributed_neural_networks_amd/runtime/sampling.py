@@ -20,6 +20,8 @@ from typing import Optional
 
 import torch
 
+from ..config import LOGPROBS_MAX_N
+
 _M32 = 0xFFFFFFFF
 
 
@@ -186,6 +188,30 @@ def apply_penalties_ref(logits: torch.Tensor, state: torch.Tensor, rep: float, f
     y = y - torch.tensor(float(pres), dtype=f32)
     x = torch.where(gen, y, x)
     return torch.where(seen, x.to(torch.bfloat16), xb)
+
+
+# ---------------------------------------------------------------------- log-probabilities
+def logprobs_ref(logits: torch.Tensor, tokens: torch.Tensor, n: int):
+    """Torch mirror of csrc/kernels/logprobs.hip: the fp64 ``log_softmax`` of
+    the (M, N) logits rounded to bf16 (the values the argmax / sampler reads:
+    after the penalties, before temperature and filters).  Returns
+    ``(chosen (M,) fp32, top_ids (M, n) int32, top_lps (M, n) fp32)`` on the
+    CPU: the log-probability of ``tokens[row]`` and the ``n`` most likely
+    entries by a stable descending sort on the kernel's ordered key of the bf16
+    bits, so equal bit patterns (common in bf16) come in ascending index order,
+    -inf entries (log-probability -inf) last, and, as on the device, +0.0
+    before -0.0 (equal as values, equal log-probabilities, distinct keys)."""
+    n = int(n)
+    xb = logits.detach().to(device="cpu", dtype=torch.bfloat16)
+    M, N = xb.shape
+    if not 0 <= n <= min(LOGPROBS_MAX_N, N):
+        raise ValueError(f"logprobs: n = {n} outside [0, {min(LOGPROBS_MAX_N, N)}]")
+    x = xb.to(torch.float64)
+    lp = torch.log_softmax(x, dim=1)
+    tok = tokens.detach().to(device="cpu", dtype=torch.int64).reshape(M)
+    chosen = lp.gather(1, tok[:, None])[:, 0].to(torch.float32)
+    order = torch.sort(_keys(xb), dim=1, descending=True, stable=True).indices[:, :n]
+    return chosen, order.to(torch.int32), lp.gather(1, order).to(torch.float32)
 
 
 def pick(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0,

@@ -393,6 +393,34 @@ class DecodeRing:
         if self.pen is not None and n_groups > 1 and not self.forward_prompt_ids:
             raise ValueError("a last stage with penalties on a ring of several groups needs forward_prompt_ids=True "
                              "on every rank (the prompt ids live on group 0)")
+        # last stage with log-probabilities (its ``logprobs`` = n >= 1): per-microbatch device histories
+        # indexed by position like ``hist``, written by the stage's own launch behind the argmax / sampler
+        # (``bind_logprobs``): lp_chosen[m][b, p] and lp_top_ids / lp_top_lps[m][b, p, :n] belong to the token
+        # sampled at position p (the prefill's first token: T - 1).  The warm-up and capture runs of
+        # ``capture`` write the positions they pass through; the positions are put back afterwards, so the
+        # real replay overwrites every one of them before ``logprobs()`` reads it, exactly as with ``hist``.
+        self.lp_n = int(getattr(self.stages[-1], "logprobs", 0) or 0) if self.last else 0
+        self.lp_chosen = self.lp_top_ids = self.lp_top_lps = None
+        self.lp_base = [0] * M  # position of the first recorded token of the current generation
+        self.lp_cnt = [0] * M  # tokens recorded since then
+        if self.lp_n:
+            if self.lanes:
+                raise ValueError("log-probabilities are not recorded with lanes (the stage's workspace serves one "
+                                 "launch at a time): use lanes=0 or logprobs=0")
+            caps = []
+            for s in self.stages:
+                c = getattr(s, "max_seq", None)
+                if c is None:
+                    from ..models import model_info
+                    cfg = model_info(s.model).cfg
+                    c = getattr(cfg, "block_size", getattr(cfg, "max_seq", 1024))
+                caps.append(int(c))
+            cap = min(caps)
+            self.lp_chosen = [torch.zeros((B, cap), dtype=torch.float32, device=dev) for _ in range(M)]
+            self.lp_top_ids = [torch.zeros((B, cap, self.lp_n), dtype=torch.int32, device=dev) for _ in range(M)]
+            self.lp_top_lps = [torch.zeros((B, cap, self.lp_n), dtype=torch.float32, device=dev) for _ in range(M)]
+            for m in range(M):
+                self.stages[-1].bind_logprobs(m * B, self.lp_chosen[m], self.lp_top_ids[m], self.lp_top_lps[m])
 
     # -- one microbatch through this rank's stages --------------------------
     def _run(self, x, m: int, T: int, out=None, advance=None):
@@ -502,6 +530,11 @@ class DecodeRing:
         for m in range(self.M):
             self.pos[m].zero_()
             self.toks[m] = []
+            if self.lp_chosen is not None:  # a new generation starts from a clean history
+                self.lp_chosen[m].zero_()
+                self.lp_top_ids[m].zero_()
+                self.lp_top_lps[m].zero_()
+                self.lp_base[m], self.lp_cnt[m] = 0, 0
         in_dt, out_dt = _act_dtype(self.stages[0]), _act_dtype(self.stages[-1])
         xin_pf = torch.empty((B * C, d), dtype=in_dt, device=self.dev) if not self.first else None
         out_pf = None
@@ -542,6 +575,8 @@ class DecodeRing:
                     pf_work[k] = self.links.nxt.isend(out_pf[k][:B * Tc])
                     n_sent += 1
                 elif final:
+                    if self.lp_chosen is not None:
+                        self.lp_base[m], self.lp_cnt[m] = T - 1, 1  # the prompt's last position gave the first token
                     if self.G == 1:
                         self.cur[m].copy_(self.out[m].view(B, 1))
                         if self.record:
@@ -639,6 +674,7 @@ class DecodeRing:
                 self.steps_done += K
                 for m in range(self.M):
                     self.hist_n[m] += K
+                    self.lp_cnt[m] += K
                 self.progress()
                 n -= K
             if n == 0:
@@ -662,6 +698,7 @@ class DecodeRing:
                     self.graphs[m]()
                 else:
                     self._decode_body(m)
+            self.lp_cnt[m] += 1
             self._send(m)
             if self.first and G > 1:
                 self.pending[m] = True
@@ -735,3 +772,23 @@ class DecodeRing:
                 parts.append(self.hist[m][:, b:b + self.hist_n[m]])
             rows.append(torch.cat(parts, 1))
         return torch.cat(rows, 0).cpu()
+
+    def logprobs(self) -> Dict[str, torch.Tensor]:
+        """The log-probabilities of the current generation, on the host and
+        aligned with ``tokens()`` (column j belongs to the j-th generated
+        token): ``chosen`` (M*B, steps) fp32, the log-probability of each
+        token under the logits it was picked from (after the penalties, before
+        temperature and filters); ``top_ids`` (M*B, steps, n) int32 and
+        ``top_lps`` (M*B, steps, n) fp32, the n most likely entries by (value
+        descending, index ascending).  Valid on the rank that holds the last
+        stage (with one group: this process); nothing travels over the
+        back-edge."""
+        if self.lp_chosen is None:
+            raise ValueError("logprobs(): this rank's last stage records none (config key 'logprobs', last group only)")
+        out = {"chosen": [], "top_ids": [], "top_lps": []}
+        for m in range(self.M):
+            b, c = self.lp_base[m], self.lp_cnt[m]
+            out["chosen"].append(self.lp_chosen[m][:, b:b + c])
+            out["top_ids"].append(self.lp_top_ids[m][:, b:b + c])
+            out["top_lps"].append(self.lp_top_lps[m][:, b:b + c])
+        return {k: torch.cat(v, 0).cpu() for k, v in out.items()}

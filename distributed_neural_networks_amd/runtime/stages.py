@@ -166,13 +166,21 @@ class TorchStage(StageCompute):
     def __init__(self, model: str, sd: Dict[str, torch.Tensor], start: int, end: int, first: bool, last: bool,
                  device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0), input_dtype: str = "fp32", input_table=None):
         from ..models import build_golden_stage
-        # sampling = (temperature, top_k, seed[, top_p, min_p[, repetition, presence, frequency penalty]])
-        if len(sampling) not in (3, 5, 8):
-            raise ValueError(f"sampling: 3, 5 or 8 entries expected, got {len(sampling)}")
+        # sampling = (temperature, top_k, seed[, top_p, min_p[, repetition, presence, frequency penalty[, logprobs]]])
+        if len(sampling) not in (3, 5, 8, 9):
+            raise ValueError(f"sampling: 3, 5, 8 or 9 entries expected, got {len(sampling)}")
         self.temperature, self.top_k, self.seed = float(sampling[0]), int(sampling[1]), int(sampling[2])
         self.top_p, self.min_p = (float(sampling[3]), float(sampling[4])) if len(sampling) >= 5 else (1.0, 0.0)
         self.rep_pen, self.pres_pen, self.freq_pen = ((float(sampling[5]), float(sampling[6]), float(sampling[7]))
-                                                      if len(sampling) == 8 else (1.0, 0.0, 0.0))
+                                                      if len(sampling) >= 8 else (1.0, 0.0, 0.0))
+        # log-probabilities (last stage): every last_only step records its token's and the top-n through
+        # the mirror (runtime/sampling.py logprobs_ref) into the histories bound to its cache rows
+        nlp = sampling[8] if len(sampling) == 9 else 0
+        from ..config import LOGPROBS_MAX_N
+        if not isinstance(nlp, int) or isinstance(nlp, bool) or not 0 <= nlp <= LOGPROBS_MAX_N:
+            raise ValueError(f"logprobs must be an integer in [0, {LOGPROBS_MAX_N}], got {nlp!r}")
+        self.logprobs = nlp if last else 0
+        self._lp_hist: Dict[int, tuple] = {}
         import math
         if not (self.rep_pen > 0 and math.isfinite(self.rep_pen)):
             raise ValueError(f"repetition penalty must be a finite number > 0, got {sampling[5]!r}")
@@ -249,6 +257,14 @@ class TorchStage(StageCompute):
         """The sample of a prefill piece before the last one is no generated token."""
         self._pen_prev[b0] = None
 
+    def bind_logprobs(self, b0: int, chosen: torch.Tensor, top_ids: torch.Tensor, top_lps: torch.Tensor) -> None:
+        """The histories of cache rows [b0, b0 + B) (``TransformerStage.bind_logprobs``):
+        fp32 (B, L), int32 (B, L, n), fp32 (B, L, n); a ``last_only`` step writes
+        position ``pos + T - 1``, the position its token was sampled at."""
+        if not self.logprobs:
+            raise ValueError("bind_logprobs: this stage records no log-probabilities")
+        self._lp_hist[b0] = (chosen, top_ids, top_lps)
+
     @torch.no_grad()
     def step(self, x, pos, B: int, T: int, b0: int = 0, out=None, last_only: bool = True):
         """KV-cached transformer step (CPU golden path; same contract as
@@ -291,6 +307,17 @@ class TorchStage(StageCompute):
                         min_p=self.min_p).to(torch.int32)
             if self.penalties_on and last_only:
                 self._pen_prev[b0] = pred.clone()
+            if self.logprobs and last_only:
+                from .sampling import logprobs_ref
+                if b0 not in self._lp_hist:
+                    raise ValueError(f"logprobs: no bind_logprobs for cache rows at {b0}")
+                chosen, top_ids, top_lps = self._lp_hist[b0]
+                q = p + T - 1
+                if 0 <= q < chosen.shape[1]:
+                    c, ti, tl = logprobs_ref(logits, pred, self.logprobs)
+                    chosen[:B, q] = c
+                    top_ids[:B, q, :self.logprobs] = ti
+                    top_lps[:B, q, :self.logprobs] = tl
             if out is not None and last_only:
                 out.copy_(pred)
                 pred = out

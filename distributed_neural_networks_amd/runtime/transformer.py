@@ -84,7 +84,7 @@ class TransformerStage(StageCompute):
                  fp8: bool = False, temperature: float = 0.0, top_k: int = 0, seed: int = 0,
                  kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
                  top_p: float = 1.0, min_p: float = 0.0, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0):
         info = model_info(model)
         # fp8 weights, prefill (W8A8) activations: "e4m3" (default) = one e4m3
         # byte per activation, per-row scale, at the fp8 MFMA rate; "split" =
@@ -121,6 +121,11 @@ class TransformerStage(StageCompute):
         if self.penalties_on and max_seq >= 32768:
             raise ValueError(f"penalties: max_seq {max_seq} >= 32768 (the 15-bit token count must not saturate "
                              f"within a generation)")
+        # log-probabilities (last stage): 1..20 = every last_only step records its token's log-probability
+        # and the top-n, by a launch of its own behind the argmax / sampler (csrc/kernels/logprobs.hip)
+        if not isinstance(logprobs, int) or isinstance(logprobs, bool) or not 0 <= logprobs <= T_.LOGPROBS_MAX_N:
+            raise ValueError(f"logprobs must be an integer in [0, {T_.LOGPROBS_MAX_N}], got {logprobs!r}")
+        self.logprobs = logprobs if last else 0
         self.model, self.family, self.cfg = model, info.family, info.cfg
         self.start, self.end, self.first, self.last = start, end, first, last
         self.device = dev = torch.device(device)
@@ -395,6 +400,46 @@ class TransformerStage(StageCompute):
             self.pen_state = torch.zeros((self.max_batch, self.Vpad), dtype=torch.int16, device=dev)
             self.pen_prev = torch.full((self.max_batch,), -1, dtype=torch.int32, device=dev)
 
+        # log-probabilities: the kernel's workspace (arrival counters, which it leaves at zero, and one
+        # launch's per-chunk partials) and the histories bound per microbatch (bind_logprobs)
+        self.lp_ws = None
+        self._lp_hist: Dict[int, tuple] = {}
+        if self.logprobs:
+            self.lp_ws = T_.logprobs_workspace(self.max_batch, self.V, self.logprobs, dev)
+
+    # ------------------------------------------------------------------ log-probabilities
+    def bind_logprobs(self, b0: int, chosen: torch.Tensor, top_ids: torch.Tensor, top_lps: torch.Tensor) -> None:
+        """The histories that steps on cache rows [b0, b0 + B) write (the caller
+        owns them, as it owns the token history): ``chosen`` fp32 (B, L),
+        ``top_ids`` int32 and ``top_lps`` fp32 (B, L, logprobs), on this device.
+        Every ``last_only`` step at these rows then records, at the position its
+        token was sampled at (``pos + T - 1``: the index the step tail uses for
+        the token), the token's log-probability and the top-n of the logits row
+        the argmax / sampler read.  The addresses are baked into captured
+        graphs: bind before a capture and keep the tensors alive."""
+        if not self.logprobs:
+            raise ValueError("bind_logprobs: this stage records no log-probabilities (logprobs = 0)")
+        n = self.logprobs
+        if (chosen.dtype != torch.float32 or chosen.dim() != 2 or top_ids.dtype != torch.int32
+                or top_lps.dtype != torch.float32 or tuple(top_ids.shape) != tuple(chosen.shape) + (n,)
+                or top_lps.shape != top_ids.shape
+                or any(t.device.type != self.device.type or not t.is_contiguous() for t in (chosen, top_ids, top_lps))):
+            raise ValueError(f"bind_logprobs: fp32 (B, L), int32 (B, L, {n}) and fp32 (B, L, {n}) on {self.device} "
+                             f"expected")
+        if b0 < 0 or b0 + chosen.shape[0] > self.max_batch:
+            raise ValueError(f"bind_logprobs: rows [{b0}, {b0 + chosen.shape[0]}) outside the {self.max_batch} rows")
+        self._lp_hist[b0] = (chosen, top_ids, top_lps)
+
+    def _record_logprobs(self, logits, tokens, b0: int, rows: int, T: int, pos, advanced: bool) -> None:
+        """The log-probability launch of a ``last_only`` step: ``tokens`` is what
+        the argmax / sampler launch just wrote; ``advanced``: that launch's fused
+        tail has already added 1 to ``pos``."""
+        hist = self._lp_hist.get(b0)
+        if hist is None or hist[0].shape[0] < rows:
+            raise ValueError(f"logprobs: no bind_logprobs covering cache rows [{b0}, {b0 + rows})")
+        T_.logprobs_rows(logits, tokens, self.V, self.logprobs, hist[0], hist[1], hist[2], self.lp_ws, pos=pos,
+                         pos_off=T - 1 - (1 if advanced else 0))
+
     # ------------------------------------------------------------------ penalties
     def penalty_begin(self, b0: int, ids: torch.Tensor) -> None:
         """Start a generation on cache rows [b0, b0 + B): clear their state and
@@ -574,6 +619,7 @@ class TransformerStage(StageCompute):
             rows, src, ldx = ntok, h, d
         logits = self.logits[r0:r0 + rows]
         pen = self.penalties_on and last_only
+        lpn = self.logprobs > 0 and last_only
         if self.fuse_norm and last_only and not self.temperature > 0 and not pen:
             # greedy: the head writes the logits and each workgroup's argmax
             # partials; one merge launch takes the ids and the step tail
@@ -582,6 +628,8 @@ class TransformerStage(StageCompute):
             also, adv, hist = _advance3(advance)
             if head_argmax(x_last, self.w_head, logits[:, :self.V], self.head_part[r0 * 2 * HEAD_PART_PER_ROW:], dst,
                            also, adv, hist):
+                if lpn:  # the head wrote the logits too
+                    self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
                 return StageOutput(logits[:, :self.V], dst)
         if self.fuse_norm:
             x_last = torch.as_strided(src, (rows, d), (ldx, 1))
@@ -610,6 +658,8 @@ class TransformerStage(StageCompute):
                     out.copy_(nxt)
                 if pen:
                     self.pen_prev[b0:b0 + rows].copy_(nxt)
+                if lpn:
+                    self._record_logprobs(logits, nxt, b0, rows, T, pos, False)
                 return StageOutput(logits[:, :self.V], nxt)
             dst = out if out is not None else nxt
             also, adv, hist = _advance3(advance)
@@ -617,6 +667,8 @@ class TransformerStage(StageCompute):
                            step=pos, also=also, advance=adv, hist=hist)
             if pen:
                 self.pen_prev[b0:b0 + rows].copy_(dst)
+            if lpn:
+                self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
             return StageOutput(logits[:, :self.V], dst)
         dst = out if (last_only and out is not None) else nxt
         also, adv, hist = _advance3(advance)
@@ -626,6 +678,8 @@ class TransformerStage(StageCompute):
             # the rows' token in a stage-owned place (the caller's `out` may change between calls): the next
             # decode step's penalty launch reads it from the same address on every graph replay
             self.pen_prev[b0:b0 + rows].copy_(dst)
+        if lpn:
+            self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
         return StageOutput(logits[:, :self.V], dst)
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None):
@@ -675,14 +729,15 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                        temperature: float = 0.0, top_k: int = 0, seed: int = 0, kv_dtype: str = "bf16",
                        kv_scale: str = "calibrated", fp8_prefill: str = "e4m3", top_p: float = 1.0,
                        min_p: float = 0.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                       frequency_penalty: float = 0.0):
+                       frequency_penalty: float = 0.0, logprobs: int = 0):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
     info = model_info(model)
     max_seq = min(max_seq, getattr(info.cfg, "block_size", getattr(info.cfg, "max_seq", max_seq)))
     return TransformerStage(model, sd, start, end, first, last, device, max_batch, max_seq, max_tokens, fp8,
                             temperature, top_k, seed, kv_dtype=kv_dtype, kv_scale=kv_scale, fp8_prefill=fp8_prefill,
                             top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                            logprobs=logprobs)
 
 
 # ---------------------------------------------------------------------- smoke / golden check

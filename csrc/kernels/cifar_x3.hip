@@ -59,6 +59,26 @@
 //    by a [3][256] table of packed bf16 hi/lo halves, copied into LDS behind
 //    the planes (116,480 B); the planes come out bit-identical to the fp32
 //    input's (see at the kernel).
+//    Issue priority: the conv2 waves carry 82 % of the MFMA cycles and, as the
+//    second-dispatched half of the workgroup, lose issue arbitration to their
+//    SIMD's conv1 wave.  Barrier stamps (s_memtime per role, a diagnostic build):
+//    conv2 work 10,120 cycles per image with the conv1 waves idle for 2,400 at
+//    the barrier.  Handing the conv2 waves the arbitration for the whole image
+//    (role swap, or one s_setprio 1) brings them to 9,000 but the conv1 waves,
+//    whose MFMAs and VALU then wait for gaps in a saturated pipe, to 11,400: the
+//    pole moves and the kernel is 5-6 % slower.  What pays is a share: a conv2
+//    wave runs the first C2_PRIO_STEPS = 9 of the 18 k-steps of each band at
+//    priority 1 and the rest, with the band's epilogue, at 0 (two s_setprio per
+//    band), and the conv1 waves issue fewer vector instructions so that they
+//    fit in what is left: image loads and boundary stores through buffer
+//    descriptors over one image (base in SGPRs, one lane offset per kernel, no
+//    64-bit per-lane arithmetic), pooled-map store offsets as lane constants plus
+//    a wave-uniform term, and conv1_store's parity branch (both sides ran, one
+//    after the other) as selects: image loop 193 -> 170 non-MFMA vector
+//    instructions (static), conv1 work 8,060 -> 6,510 cycles.  Neither half wins
+//    alone (partial priority on the old addressing +1.1 %, lean addressing
+//    alone a tie); together conv1 9,140 / conv2 9,660 cycles and -2.5 to -2.9 %
+//    in every interleaved round (profiles/cifar_s0_arb_ab.jsonl).
 //  * cifar_fc1_x3_kernel: fc1 + bias + ReLU on the fp32 boundary tensor, the
 //    split done in registers while staging A (no split copy in HBM): 256x256x32
 //    tiles, 8 waves of 128x64, per k32 step 3 x 32 mfma_f32_16x16x32_bf16 per
@@ -121,6 +141,29 @@ __device__ __forceinline__ float4 buf_load16(const void* base, int bytes, int vo
   return float4{};
 #endif
 }
+// the 4-B load and the 16-B / 8-B stores of the same addressing (a store past ``bytes`` is dropped)
+__device__ __forceinline__ uint32_t buf_load4(const void* base, int bytes, int voff, int soff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
+  return __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0);
+#else
+  return 0;
+#endif
+}
+__device__ __forceinline__ void buf_store16(void* base, int bytes, int voff, int soff, uint4 v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(u32x4{v.x, v.y, v.z, v.w}, rsrc, voff, soff, 0);
+#endif
+}
+__device__ __forceinline__ void buf_store8(void* base, int bytes, int voff, int soff, uint2 v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b64(u32x2{v.x, v.y}, rsrc, voff, soff, 0);
+#endif
+}
 // the same load as LDS DMA (glds16's layout: lane l lands at lds_wave_base + 16 l)
 __device__ __forceinline__ void buf_glds16(const void* base, int bytes, int voff, int soff, void* lds_wave_base) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -137,6 +180,10 @@ constexpr int XPL = 34 * XW * 8;              // 10880: one input plane
 constexpr int A1PL = 18 * 18 * 64;            // 20736: one pooled-conv1 plane [18][18][32] bf16
 constexpr int XP32 = 224;                     // C1 = 1: xin row pitch in bytes (56 dwords, 103 bf16 used)
 constexpr int XPL32 = 34 * XP32;              // 7616: one channel-packed input plane
+// Issue arbitration between the two waves of a SIMD (the conv1 wave and the conv2 wave): a conv2
+// wave runs the first C2_PRIO_STEPS of the 18 k-steps of each band at s_setprio 1 and the rest,
+// with the band's epilogue, at 0 ("Issue priority" in the header).
+constexpr int C2_PRIO_STEPS = 9;
 
 // C1: conv1 producer path.  0: HWC4 planes, K = 48; 1: channel-packed planes, K = 32.
 template <int C1>
@@ -191,6 +238,7 @@ __device__ __forceinline__ void c2_issue(const uint32_t (&b)[3][2], bf16x8 (&a)[
 template <int S>
 __device__ __forceinline__ void c2_step(const uint32_t (&b)[3][2], const bf16x8 (&wh)[18], const bf16x8 (&wl)[18],
                                         f32x16 (&acc)[2], bf16x8 (&cur)[4], bf16x8 (&nxt)[4]) {
+  if constexpr (S == C2_PRIO_STEPS) __builtin_amdgcn_s_setprio(0);
   if constexpr (S + 1 < 18) {
     c2_issue<S + 1>(b, nxt);
     asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
@@ -253,6 +301,7 @@ template <int T>
 __device__ __forceinline__ void m16_step(const uint32_t (&b)[2], const bf16x8 (&wh)[2][9], const bf16x8 (&wl)[2][9],
                                          f32x4 (&acc)[4][2], bf16x8 (&cur)[4], bf16x8 (&nxt)[4]) {
   constexpr int tap = T >> 1, m0 = 2 * (T & 1);
+  if constexpr (T == C2_PRIO_STEPS) __builtin_amdgcn_s_setprio(0);
   if constexpr (T + 1 < 18) {
     m16_issue<T + 1>(b, nxt);
     asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
@@ -278,8 +327,13 @@ __device__ __forceinline__ void m16_step(const uint32_t (&b)[2], const bf16x8 (&
 // same (oc, PY); one v_permlane16_swap per dword hands the even row columns
 // 0-3 and the odd row columns 4-7: one 16-B store per lane (8-B hi + 8-B lo in
 // the blocked encoding, the split of the same fp32 values).
+// The stores go through a buffer descriptor over the image's 16 KiB of the boundary: ``lane`` is
+// the lane's byte offset at band 0 and N tile 0 (computed once per kernel), the band p and the N
+// tile go into the scalar offset, so a store costs no per-lane address arithmetic.
+//   fp32:  4*(oc*64 + PY*8 + 4*x1),  PY = 4*(rw>>1) + 2*p + y1  ->  lane + 64*p + 4096*NT
+//   split: (oc*2 + (PY>>2))*128 + ((PY&3)*8 + 4*x1)*2           ->  lane + 32*p + 4096*NT  (lo: + 64)
 template <bool SPLIT_OUT, int NT>
-__device__ __forceinline__ void m16_epilogue(const f32x4 (&acc)[4][2], float bias, float* img, int oc, int PY, int x1) {
+__device__ __forceinline__ void m16_epilogue(const f32x4 (&acc)[4][2], float bias, float* img, int lane, int p) {
   float v[4];
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) {
@@ -288,15 +342,14 @@ __device__ __forceinline__ void m16_epilogue(const f32x4 (&acc)[4][2], float bia
   }
   const auto s0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[0]), __float_as_uint(v[2]), false, false);
   const auto s1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[1]), __float_as_uint(v[3]), false, false);
-  if constexpr (SPLIT_OUT) {  // k = oc*64 + PY*8 + 4*x1 + 0..3
+  if constexpr (SPLIT_OUT) {
     uint2 hi, lo;
     split2<true>(__uint_as_float(s0[0]), __uint_as_float(s0[1]), hi.x, lo.x);
     split2<true>(__uint_as_float(s1[0]), __uint_as_float(s1[1]), hi.y, lo.y);
-    char* bp = reinterpret_cast<char*>(img) + (oc * 2 + (PY >> 2)) * 128 + ((PY & 3) * 8 + 4 * x1) * 2;
-    *reinterpret_cast<uint2*>(bp) = hi;
-    *reinterpret_cast<uint2*>(bp + 64) = lo;
+    buf_store8(img, 16384, lane, 32 * p + 4096 * NT, hi);
+    buf_store8(img, 16384, lane, 32 * p + 4096 * NT + 64, lo);
   } else {
-    *reinterpret_cast<uint4*>(img + oc * 64 + PY * 8 + 4 * x1) = make_uint4(s0[0], s0[1], s1[0], s1[1]);
+    buf_store16(img, 16384, lane, 64 * p + 4096 * NT, make_uint4(s0[0], s0[1], s1[0], s1[1]));
   }
 }
 
@@ -351,21 +404,28 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
     const int q = ((r32 & 1) ? 2 : 0) + ((r32 & 2) ? 1 : 0);
     const int cb = r32 & ~3;
 
-    // v = bias + ReLU + 2x2 max-pool of the lane's 2x2 pooled pixels (Y0 + qy, X0 + qx) of
-    // channel r32: quad-DPP gather of 4 channels of one pooled pixel per lane, hi/lo split,
-    // one 8-B store per plane
-    auto conv1_store = [&](const float (&v)[4], int Y0, int X0, int k) {
+    // The pooled-map store offset of a lane is (Y*18 + X)*64 + (((cb>>3) ^ swizzle(Y)) << 4) + 2*(cb&7) at
+    // pooled pixel (Y, X) = (Y0 + (q>>1), X0 + (q&1) + xh), Y0 = 2*ty + 1.  a1_lane(par, xh) is its
+    // lane part, computed once, for tiles whose row index ty has parity par (the chunk XOR depends on
+    // ty through that parity only); the rest, (Y0*18 + X0)*64 and the slot, is wave-uniform.
+    auto a1_lane = [&](int par, int xh) {
+      const int Y = 2 * par + 1 + (q >> 1);
+      return ((q >> 1) * 18 + (q & 1) + xh) * 64 + ((((cb >> 3) ^ a1_swz<C2>(Y))) << 4) + (cb & 7) * 2;
+    };
+    // v = bias + ReLU + 2x2 max-pool of the lane's 2x2 pooled pixels of channel r32: quad-DPP gather
+    // of 4 channels of one pooled pixel per lane, hi/lo split, one 8-B store per plane at
+    // ob = a1_lane + the hi plane of the slot + the uniform (Y0*18 + X0)*64 of the call
+    auto conv1_store = [&](const float (&v)[4], int ob) {
       const bool odd = r32 & 1;
       const int s0 = __float_as_int(odd ? v[0] : v[2]), s1 = __float_as_int(odd ? v[1] : v[3]);
       const float r0 = __int_as_float(dpp_xor1(s0)), r1 = __int_as_float(dpp_xor1(s1));
       uint32_t u0h, u0l, u1h, u1l;
-      if (!odd) {
-        split2<true>(v[0], r0, u0h, u0l);
-        split2<true>(v[1], r1, u1h, u1l);
-      } else {
-        split2<true>(r0, v[2], u0h, u0l);
-        split2<true>(r1, v[3], u1h, u1l);
-      }
+      // even lane: (v[0], r0), (v[1], r1); odd lane: (r0, v[2]), (r1, v[3]).  The operands are
+      // selected and each pair split once: a branch on the lane's parity runs both sides of the
+      // split one after the other
+      const float k0 = odd ? v[2] : v[0], k1 = odd ? v[3] : v[1];
+      split2<true>(odd ? r0 : k0, odd ? k0 : r0, u0h, u0l);
+      split2<true>(odd ? r1 : k1, odd ? k1 : r1, u1h, u1l);
       const bool hi2 = r32 & 2;
       const uint32_t rch = (uint32_t)dpp_xor2((int)(hi2 ? u0h : u1h));
       const uint32_t rcl = (uint32_t)dpp_xor2((int)(hi2 ? u0l : u1l));
@@ -375,10 +435,8 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       wh.y = hi2 ? mh : rch;
       wl.x = hi2 ? rcl : ml;
       wl.y = hi2 ? ml : rcl;
-      const int Y = Y0 + (q >> 1), X = X0 + (q & 1);
-      const int o = (Y * 18 + X) * 64 + ((((cb >> 3) ^ a1_swz<C2>(Y))) << 4) + (cb & 7) * 2;
-      *reinterpret_cast<uint2*>(smem + a1_off<C1>(k, 0) + o) = wh;
-      *reinterpret_cast<uint2*>(smem + a1_off<C1>(k, 1) + o) = wl;
+      *reinterpret_cast<uint2*>(smem + ob) = wh;
+      *reinterpret_cast<uint2*>(smem + ob + A1PL) = wl;
     };
     // one barrier per image: conv1 of image it, then staging of image it+1 from the prefetch registers
     auto produce = [&](auto&& load_img, auto&& stage_img, auto&& conv1_img) {
@@ -411,12 +469,14 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       resident_fence(w1lf);
 
       float pf[4][3];
+      // a buffer descriptor over image k alone (scalar arithmetic), one lane offset for the kernel
       auto load_img = [&](int k) {
         const float* xb = x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int c = 0; c < 3; ++c) pf[i][c] = xb[c * 1024 + rt + 256 * i];
+          for (int c = 0; c < 3; ++c)
+            pf[i][c] = __uint_as_float(buf_load4(xb, 12288, 4 * rt, 4 * (c * 1024 + 256 * i)));
       };
       auto stage_img = [&](int k) {  // prefetch registers -> padded HWC4 hi / lo planes
         char* xh = smem + xin_off<C1>(k, 0);
@@ -435,7 +495,9 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       const int c1_lane = ((r32 >> 3) * XW + (r32 & 7) + 2 * h) * 8;
 
       // bias + ReLU + 2x2 max-pool in registers (max(a)+b == max(a+b) exactly)
-      auto conv1_epi = [&](int t, const f32x16& acc, int k) {
+      // tile t = rw + 8 j has an even row index ty = 2 j, its pair partner t + 4 the odd 2 j + 1
+      const int a1l[2] = {a1_lane(0, 2 * h), a1_lane(1, 2 * h)};
+      auto conv1_epi = [&](int t, const f32x16& acc, int k, int par) {
         const int ty = t >> 2, tx = t & 3;
         float v[4];
 #pragma unroll
@@ -446,7 +508,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
             v[qy * 2 + qx] =
                 fmaxf(fmax_nan(fmax_nan(acc[g0], acc[g0 + 1]), fmax_nan(acc[g0 + 4], acc[g0 + 5])) + bias, 0.f);
           }
-        conv1_store(v, 2 * ty + 1, 4 * tx + 2 * h + 1, k);
+        conv1_store(v, a1l[par] + a1_off<C1>(k, 0) + ((2 * ty + 1) * 18 + 4 * tx + 1) * 64);
       };
       auto frag = [&](const char* p) {
         const uint2 a = *reinterpret_cast<const uint2*>(p);
@@ -476,8 +538,8 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
           acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[s], w1hf[s], acca, 0, 0, 0);
           accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fbl[s], w1hf[s], accb, 0, 0, 0);
         }
-        conv1_epi(ta, acca, k);
-        conv1_epi(tb, accb, k);
+        conv1_epi(ta, acca, k, 0);
+        conv1_epi(tb, accb, k, 1);
       };
       produce(load_img, stage_img, [&](int it) {
 #pragma unroll 1
@@ -506,15 +568,21 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       const int sy = (r5 & ~3) | ((r5 & 1) << 1) | ((r5 >> 1) & 1);
       // the input prefetch: three float4 (IN = 0) or three dwords of bytes (IN = 1)
       std::conditional_t<IN == 1, uint32_t, float4> pf[3];
+      // Loads go through a buffer descriptor over image k alone: its base is scalar arithmetic (no
+      // 32-bit limit on the batch), the lane's offset inside an image is computed once, and nothing
+      // per lane is 64-bit.  The image index is in range by construction (k < n), and a lane's
+      // bytes end at the image's last byte at most.
+      // IN = 1: bytes 12 sj .. 12 sj + 11 of row sy: pixels 4 sj .. 4 sj + 3, HWC
+      const int ld_lane = IN == 1 ? sy * 96 + sj * 12 : (sy * 32 + sj * 4) * 4;
       auto load_img = [&](int k) {
-        if constexpr (IN == 1) {  // bytes 12 sj .. 12 sj + 11 of row sy: pixels 4 sj .. 4 sj + 3, HWC
-          const unsigned char* xb = x.x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072 + sy * 96 + sj * 12;
+        if constexpr (IN == 1) {
+          const unsigned char* xb = x.x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072;
 #pragma unroll
-          for (int c = 0; c < 3; ++c) pf[c] = *reinterpret_cast<const uint32_t*>(xb + 4 * c);
+          for (int c = 0; c < 3; ++c) pf[c] = buf_load4(xb, 3072, ld_lane, 4 * c);
         } else {
-          const float* xb = x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072 + sy * 32 + sj * 4;
+          const float* xb = x + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 3072;
 #pragma unroll
-          for (int c = 0; c < 3; ++c) pf[c] = *reinterpret_cast<const float4*>(xb + c * 1024);
+          for (int c = 0; c < 3; ++c) pf[c] = buf_load16(xb, 12288, ld_lane, c * 4096);
         }
       };
       auto stage_img = [&](int k) {  // prefetch registers -> padded channel-packed hi / lo planes
@@ -565,6 +633,8 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
       for (int i = 0; i < 4; ++i)
         l1[i] = h ? (rr + (i < 2 ? i : 2)) * XP32 + 12 * cc + 16 : (rr + 1) * XP32 + 12 * cc + 4 * i;
       auto ld32 = [&](const char* p) { return *reinterpret_cast<const uint32_t*>(p); };
+      // a wave's tile pairs tp = rw + 4 j all have row indices ty = (rw >> 1) + 2 j of one parity
+      const int a1l = a1_lane((rw >> 1) & 1, 4 * h);
       // the even and the odd tile of 4 rows x 16 columns: 32 dword reads up front, two
       // accumulation chains interleaved, the 2x2 pool across the two accumulators
       auto conv1_pair = [&](int tp, int k) {
@@ -603,7 +673,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
               v[qy * 2 + qx] =
                   fmaxf(fmax_nan(fmax_nan(acca[g], accb[g]), fmax_nan(acca[g + 4], accb[g + 4])) + bias, 0.f);
             }
-          conv1_store(v, 2 * ty + 1, 8 * tx2 + 4 * h + 2 * e + 1, k);
+          conv1_store(v, a1l + a1_off<C1>(k, 0) + ((2 * ty + 1) * 18 + 8 * tx2 + 2 * e + 1) * 64);
         }
       };
       produce(load_img, stage_img, [&](int it) {
@@ -635,6 +705,9 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
 #pragma unroll
     for (int kyp = 0; kyp < 2; ++kyp) lb[kyp] = (uint32_t)((py * 18 + px) * 64 + ((q16 ^ a1_swz<C2>(py + kyp)) << 4));
 
+    // the lane's byte offset inside an image's boundary at band 0 and N tile 0 (m16_epilogue)
+    const int st_lane = SPLIT_OUT ? (oc * 2 + (rw >> 1)) * 128 + (y1 * 8 + 4 * x1) * 2
+                                  : (oc * 64 + ((rw >> 1) * 4 + y1) * 8 + 4 * x1) * 4;
     auto conv2_img = [&](int k) {  // conv2 + bias + ReLU + pool of image k -> out
       float* img = out + (size_t)(blockIdx.x + (size_t)k * gridDim.x) * 4096;
       const uint32_t plane = (uint32_t)(uintptr_t)(smem + a1_off<C1>(k, 0));
@@ -647,10 +720,11 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) acc[mt][0] = acc[mt][1] = f32x4{};
         bf16x8 a0[4], a1[4];
+        __builtin_amdgcn_s_setprio(1);  // back to 0 inside m16_step<C2_PRIO_STEPS>
         m16_issue<0>(b, a0);
         m16_step<0>(b, w2hf, w2lf, acc, a0, a1);
-        m16_epilogue<SPLIT_OUT, 0>(acc, bias0, img, oc, 2 * ty2 + y1, x1);
-        m16_epilogue<SPLIT_OUT, 1>(acc, bias1, img, oc + 16, 2 * ty2 + y1, x1);
+        m16_epilogue<SPLIT_OUT, 0>(acc, bias0, img, st_lane, p);
+        m16_epilogue<SPLIT_OUT, 1>(acc, bias1, img, st_lane, p);
       }
     };
 
@@ -696,6 +770,7 @@ __global__ __launch_bounds__(512, 1) void cifar_stage0_x3_kernel(
           for (int par = 0; par < 2; ++par) b[ky][par] = rb + lb[ky][par];
         f32x16 acc[2] = {f32x16{}, f32x16{}};
         bf16x8 a0[4], a1[4];
+        __builtin_amdgcn_s_setprio(1);  // back to 0 inside c2_step<C2_PRIO_STEPS>
         c2_issue<0>(b, a0);
         c2_step<0>(b, w2hf, w2lf, acc, a0, a1);
         if constexpr (WIDE) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Decode attention at the decode benches' shapes, batched kernel vs the
-one-pass kernel and its switches (attention.hip attn_decode_1p_kernel).
+one-pass kernel (attention.hip attn_decode_1p_kernel), by default and forced.
 
 The K/V caches rotate over enough copies (> 640 MB) that every launch streams
 from HBM as in a real decode step (one layer's cache is evicted from the
@@ -33,13 +33,8 @@ VARIANTS = {  # name: env
     "batched": {"DNN_DECODE_1P": "0"},
     "1p": {"DNN_DECODE_1P": "1"},
     "1p_force": {"DNN_DECODE_1P": "2"},
-    "1p_kf0": {"DNN_DECODE_1P": "1", "DNN_DECODE_1P_KF": "0"},
-    "1p_kf1": {"DNN_DECODE_1P": "1", "DNN_DECODE_1P_KF": "1"},
-    "1p_knt0": {"DNN_DECODE_1P": "1", "DNN_DECODE_1P_KNT": "0"},
-    "1p_knt1": {"DNN_DECODE_1P": "1", "DNN_DECODE_1P_KNT": "1"},
-    "1p_rs0": {"DNN_DECODE_1P": "1", "DNN_DECODE_1P_RS": "0"},
 }
-KEYS = ("DNN_DECODE_1P", "DNN_DECODE_1P_KNT", "DNN_DECODE_1P_RS", "DNN_DECODE_1P_KF")
+KEYS = ("DNN_DECODE_1P",)
 
 
 def main():

@@ -33,8 +33,6 @@ def apply(switch: str, v: int) -> None:
         gemm.set_stream_gemm(v)
     elif switch == "decode_1p":  # one-pass decode attention: 0 batched kernel, 1 default, 2 forced (attention.hip)
         os.environ["DNN_DECODE_1P"] = str(v)
-    elif switch == "decode_1p_kf":  # one-pass decode attention: K/V loads issued before q (attention.hip KF)
-        os.environ["DNN_DECODE_1P_KF"] = str(v)
     elif switch == "epi_pre":  # decode GEMM epilogue operands issued with the first loads (gemm_oneshot.h / skinny)
         lib().gemm_set_epi_prefetch(v)
     elif switch == "os_lds_floor":  # one-shot launch LDS floor in bytes (gemm_skinny.hip g_os_lds_floor; 0 = own size)

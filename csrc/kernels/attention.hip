@@ -854,8 +854,22 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
 //      split) or as the (o, m, l) partial decode_combine_kernel merges.
 // Cache rows past the runtime length are never scored: their loads are
 // clamped to the last valid row (same address: coalesced).
-template <int HD, int G, int FM, bool NT, int NW, int KT, int VE, int VU, bool RS = false, bool KNT = NT,
-          bool KF = false>
+//
+// Three rules follow from the group size G alone (each was an A/B switch; the
+// losing arms are deleted, profiles/attention_1p_arms_removed.md):
+//   RS = G == 1: scores in the row layout (thread = 8 dims of key rows grp +
+//     GPB*u, dot2 + DPP row sum, as the value rows) for MHA, MFMA key tiles
+//     for GQA.  At MHA hd 64 an MFMA tile uses 1 of 16 head columns and its
+//     half-row key loads ran 10 % slower than whole rows (GPT-2 B=64 22.0 vs
+//     19.9 us, profiles/r3_attn_1p_probe.jsonl); the row layout for GQA
+//     measured 22.3 vs 19.0 us at Llama-3 B=32 and was never built.
+//   KNT = NT && RS: the key loads non-temporal (NT: the value loads) for MHA,
+//     default policy for GQA (Llama-3 B=32 19.54 -> 19.11 us; GPT-2 B=64
+//     19.28 -> 20.01 us the other way).
+//   KF = !RS: K/V loads issued before q for GQA (Llama-3 B=32 19.40 -> 19.12
+//     us, decode 3.930 -> 3.902 ms/step), after q for MHA (GPT-2 B=64 19.50
+//     -> 19.91 us the other way; profiles/r3_attn_1p_probe_v3.jsonl).
+template <int HD, int G, int FM, bool NT, int NW, int KT, int VE, int VU>
 __global__ __launch_bounds__(NW * 64) void attn_decode_1p_kernel(const bf16_t* __restrict__ q, int ldq,
                                                                bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
                                                                float* __restrict__ ws, int H, int Hkv, int S,
@@ -863,9 +877,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_1p_kernel(const bf16_t* _
                                                                const float* __restrict__ cosT,
                                                                const float* __restrict__ sinT, float scale_log2,
                                                                bf16_t* __restrict__ o_direct) {
-  // RS: scores in the row layout (thread = 8 dims of key rows grp + GPB*u, dot2
-  // + DPP row sum, as the value rows) instead of MFMA key tiles; KNT: the key
-  // loads non-temporal (NT: the value loads)
+  constexpr bool RS = G == 1, KNT = NT && RS, KF = !RS;
   constexpr bool FUSED = FM != 0, ROPE = FM == 2;
   constexpr int NTH = NW * 64;
   constexpr int LPK = HD / 8;          // lanes per value row (16 B = 8 dims each)
@@ -1356,47 +1368,6 @@ static void launch_decode_combine(const float* ws, bf16_t* o, int B, int H, int 
   hipLaunchKernelGGL(decode_combine_kernel, dim3(B * H), dim3(128), 0, st, ws, o, B, H, Hkv, hd, ns);
 }
 
-struct Dec1pArgs {
-  const bf16_t* q;
-  int ldq;
-  bf16_t *kc, *vc;
-  float* ws;
-  int H, Hkv, S;
-  const int* lens;
-  const float *cosT, *sinT;
-  float sl2;
-  bf16_t* o;
-  bool kf;  // K/V loads issued before q (attn_decode_1p_kernel KF)
-};
-template <int HD, int G, int NW, int KT, int VE, int VU, bool RS, int FM, bool NT, bool KNT>
-static void launch_1p_k(const Dec1pArgs& a, dim3 grid, hipStream_t st) {
-  const size_t smem = sizeof(float) * (size_t)NW * G * (HD + 1);  // [NW][G][HD] + [NW][G] (step 6)
-  if (a.kf)
-    hipLaunchKernelGGL((attn_decode_1p_kernel<HD, G, FM, NT, NW, KT, VE, VU, RS, KNT, true>), grid, dim3(NW * 64),
-                       smem, st, a.q, a.ldq, a.kc, a.vc, a.ws, a.H, a.Hkv, a.S, a.lens, a.cosT, a.sinT, a.sl2, a.o);
-  else
-    hipLaunchKernelGGL((attn_decode_1p_kernel<HD, G, FM, NT, NW, KT, VE, VU, RS, KNT, false>), grid, dim3(NW * 64),
-                       smem, st, a.q, a.ldq, a.kc, a.vc, a.ws, a.H, a.Hkv, a.S, a.lens, a.cosT, a.sinT, a.sl2, a.o);
-}
-template <int HD, int G, int NW, int KT, int VE, int VU, bool RS, int FM>
-static void launch_1p_f(const Dec1pArgs& a, bool nt, bool knt, dim3 grid, hipStream_t st) {
-  if (!nt)
-    launch_1p_k<HD, G, NW, KT, VE, VU, RS, FM, false, false>(a, grid, st);
-  else if (knt)
-    launch_1p_k<HD, G, NW, KT, VE, VU, RS, FM, true, true>(a, grid, st);
-  else
-    launch_1p_k<HD, G, NW, KT, VE, VU, RS, FM, true, false>(a, grid, st);
-}
-template <int HD, int G, int NW, int KT, int VE, int VU, bool RS>
-static void launch_1p(const Dec1pArgs& a, int fm, bool nt, bool knt, dim3 grid, hipStream_t st) {
-  if (fm == 2)
-    launch_1p_f<HD, G, NW, KT, VE, VU, RS, 2>(a, nt, knt, grid, st);
-  else if (fm == 1)
-    launch_1p_f<HD, G, NW, KT, VE, VU, RS, 1>(a, nt, knt, grid, st);
-  else
-    launch_1p_f<HD, G, NW, KT, VE, VU, RS, 0>(a, nt, knt, grid, st);
-}
-
 // One-pass decode attention (bf16 cache): returns 1 when the shape is not
 // covered (the caller falls back to the batched kernel).  Splits of at most
 // DEC1P_CAP keys; more than one split only when the caller's workspace holds
@@ -1420,32 +1391,22 @@ static int attn_decode_1p_launch(const void* q, int ldq, void* kc, void* vc, voi
   // profiles/r3_attn_1p_shapes.jsonl); MHA's 4-wave workgroups are small
   if (!force && ns_min <= 1 && G > 1 && (long)B * Hkv * ns > 256) return 1;
   dim3 grid(B * Hkv, ns);
-  // row-layout scores for MHA, MFMA key tiles for GQA: at MHA hd 64 an MFMA tile
-  // uses 1 of 16 head columns and its half-row key loads ran 10 % slower than
-  // whole rows (GPT-2 B=64 22.0 vs 19.9 us, profiles/r3_attn_1p_probe.jsonl)
-  const char* rs_e = getenv("DNN_DECODE_1P_RS");    // A/B override: 0 MFMA tiles, 1 row layout
-  const char* kn_e = getenv("DNN_DECODE_1P_KNT");   // key loads non-temporal (A/B; default: as the values)
-  const bool rs = rs_e != nullptr ? atoi(rs_e) == 1 : G == 1;
-  // key loads: non-temporal for MHA, default policy for GQA (Llama-3 B=32
-  // 19.54 -> 19.11 us; GPT-2 B=64 19.28 -> 20.01 the other way)
-  const bool knt = nt && (kn_e != nullptr ? atoi(kn_e) != 0 : G == 1);
-  // K/V loads before q for GQA (Llama-3 B=32 19.40 -> 19.12 us, decode 3.930 -> 3.902 ms/step), after q for
-  // MHA (GPT-2 B=64 19.50 -> 19.91 us the other way; profiles/r3_attn_1p_probe_v3.jsonl)
-  const char* kf_e = getenv("DNN_DECODE_1P_KF");    // A/B override: 1 before q, 0 after
-  const bool kf = kf_e != nullptr ? atoi(kf_e) == 1 : G > 1;
-  Dec1pArgs a{(const bf16_t*)q, ldq, (bf16_t*)kc, (bf16_t*)vc, ws, H, Hkv, S, lens, cosT, sinT, sl2, (bf16_t*)o, kf};
-  // hd 128 GQA (Llama-3 G = 4, llama3-tiny G = 2): 8 waves x 5 key tiles; hd 64 MHA (GPT-2): 4 waves x 10
-  // (row-layout scores for GQA measured 22.3 vs 19.0 us at Llama-3 B=32: not built)
-  if (hd == 128 && G == 4)
-    launch_1p<128, 4, 8, 5, 8, 20, false>(a, fm, nt, knt, grid, st);
-  else if (hd == 128 && G == 2)
-    launch_1p<128, 2, 8, 5, 8, 20, false>(a, fm, nt, knt, grid, st);
-  else if (hd == 64 && G == 1 && rs)
-    launch_1p<64, 1, 4, 10, 2, 20, true>(a, fm, nt, knt, grid, st);
-  else if (hd == 64 && G == 1)
-    launch_1p<64, 1, 4, 10, 6, 20, false>(a, fm, nt, knt, grid, st);
+  // hd 128 GQA (Llama-3 G = 4, llama3-tiny G = 2): 8 waves x 5 key tiles; hd 64 MHA (GPT-2): 4 waves, 20 key
+  // rows per thread (row-layout scores: VU sets the split capacity, KT is unused).  Dynamic LDS: the reduction's
+  // [NW][G][HD] + [NW][G]
+#define DEC1P(HDV, GV, NWV, KTV, VEV, VUV, FMV, NTV)                                                                  \
+  if (hd == HDV && G == GV && fm == FMV && nt == NTV)                                                                 \
+    hipLaunchKernelGGL((attn_decode_1p_kernel<HDV, GV, FMV, NTV, NWV, KTV, VEV, VUV>), grid, dim3(NWV * 64),          \
+                       sizeof(float) * (size_t)NWV * GV * (HDV + 1), st, (const bf16_t*)q, ldq, (bf16_t*)kc,          \
+                       (bf16_t*)vc, ws, H, Hkv, S, lens, cosT, sinT, sl2, (bf16_t*)o);                                \
   else
-    return 1;
+#define DEC1P_SHAPE(HDV, GV, NWV, KTV, VEV, VUV)                                                                      \
+  DEC1P(HDV, GV, NWV, KTV, VEV, VUV, 0, false) DEC1P(HDV, GV, NWV, KTV, VEV, VUV, 0, true)                            \
+  DEC1P(HDV, GV, NWV, KTV, VEV, VUV, 1, false) DEC1P(HDV, GV, NWV, KTV, VEV, VUV, 1, true)                            \
+  DEC1P(HDV, GV, NWV, KTV, VEV, VUV, 2, false) DEC1P(HDV, GV, NWV, KTV, VEV, VUV, 2, true)
+  DEC1P_SHAPE(128, 4, 8, 5, 8, 20) DEC1P_SHAPE(128, 2, 8, 5, 8, 20) DEC1P_SHAPE(64, 1, 4, 10, 2, 20) { return 1; }
+#undef DEC1P_SHAPE
+#undef DEC1P
   if (ns > 1)
     launch_decode_combine(ws, (bf16_t*)o, B, H, Hkv, hd, ns, st);
   return (int)hipGetLastError();

@@ -1,8 +1,8 @@
 """Every decode-attention route held to the selector fixtures of tests/attn_exact.py
 (MI355X only): the batched split-K kernel (DPP scores at MHA, MFMA scores at
 GQA; head-major q, fused QKV rows, fused + RoPE; bf16 and e4m3 caches), the
-one-pass kernel with its RS / KF / KNT switches and forced split counts, both
-combine kernels, and the non-temporal instantiations.
+one-pass kernel (MFMA scores at GQA, row-layout scores at MHA) with forced
+split counts, both combine kernels, and the non-temporal instantiations.
 
 Each (sequence, head) selects a hand-placed set of 1, 2, 4, 8 or 16 keys: key
 0, key len - 1 (the new key of a fused step), both sides of every split
@@ -141,14 +141,12 @@ def test_e4m3_refuses_gqa_at_hd64():
 # ---------------------------------------------------------------------------------------------------------------
 # the one-pass kernel
 # ---------------------------------------------------------------------------------------------------------------
-def _one_pass(monkeypatch, rs=None, kf=None, knt=None, ns=None):
+def _one_pass(monkeypatch, ns=None):
     monkeypatch.setenv("DNN_DECODE_1P", "2")
-    for key, val in (("DNN_DECODE_1P_RS", rs), ("DNN_DECODE_1P_KF", kf), ("DNN_DECODE_1P_KNT", knt),
-                     ("DNN_DECODE_1P_NS", ns)):
-        if val is None:
-            monkeypatch.delenv(key, raising=False)
-        else:
-            monkeypatch.setenv(key, str(val))
+    if ns is None:
+        monkeypatch.delenv("DNN_DECODE_1P_NS", raising=False)
+    else:
+        monkeypatch.setenv("DNN_DECODE_1P_NS", str(ns))
 
 
 def _1p_lens(S, fused):
@@ -164,21 +162,21 @@ def _assert_one_pass_ran(fx, ws, ns, ws_splits):
 
 
 @pytest.mark.parametrize("S,force_ns", [(641, None), (1300, None), (600, 2), (600, 3)])
-@pytest.mark.parametrize("hd,G,rs", [(128, 4, None), (128, 2, None), (128, 2, 1), (64, 1, 1), (64, 1, 0)])
-def test_one_pass(hd, G, rs, S, force_ns, monkeypatch):
-    """The four shapes attn_decode_1p_launch takes, ns from the capacity (641 -> 2, 1300 -> 3) or forced, lengths
-    around the 640-key split capacity, K/V issued before and after q (KF), every FM.  RS picks the row-layout or
-    the MFMA scores at hd 64; the GQA shapes are built with MFMA scores only and ignore it."""
+# explicit ids: the ids these three shapes have always had
+@pytest.mark.parametrize("hd,G", [pytest.param(128, 4, id="128-4-None"), pytest.param(128, 2, id="128-2-None"),
+                                  pytest.param(64, 1, id="64-1-1")])
+def test_one_pass(hd, G, S, force_ns, monkeypatch):
+    """The three shapes attn_decode_1p_launch takes (GQA: MFMA scores, K/V issued before q; MHA: row-layout
+    scores, K/V after q), ns from the capacity (641 -> 2, 1300 -> 3) or forced, lengths around the 640-key split
+    capacity, every FM."""
     Hkv = 2
     ns = force_ns or -(-S // 640)
     for fused, rope in FMS:
         lens = _1p_lens(S, fused)
         fx = ax.decode(len(lens), G * Hkv, Hkv, hd, S, lens, ns, fused, rope, edges=(16, 128, 320))
-        for kf in (0, 1):
-            for knt in ((None, 1) if kf == 0 else (0,)):  # KNT only acts on non-temporal launches: a no-op here
-                _one_pass(monkeypatch, rs=rs, kf=kf, knt=knt, ns=force_ns)
-                ws, _ = _run(fx, ws_splits=ns + 2, who=f"FM={int(fused) + int(rope)} KF={kf} KNT={knt}")
-                _assert_one_pass_ran(fx, ws, ns, ns + 2)
+        _one_pass(monkeypatch, ns=force_ns)
+        ws, _ = _run(fx, ws_splits=ns + 2, who=f"FM={int(fused) + int(rope)}")
+        _assert_one_pass_ran(fx, ws, ns, ns + 2)
 
 
 @pytest.mark.parametrize("hd,G", [(64, 2), (128, 1), (128, 8)])
@@ -225,17 +223,18 @@ def test_non_temporal_batched_e4m3(G, monkeypatch):
     _run(fx, kv8=True, who="NT e4m3")
 
 
-@pytest.mark.parametrize("hd,G,rs,S", [(128, 4, None, 4097), (64, 1, 1, 8193), (64, 1, 0, 8193)])
-def test_non_temporal_one_pass(hd, G, rs, S, monkeypatch):
-    """ns = 7 (fast combine) and 13 (the loop combine kernel) from the capacity; key loads both ways (KNT)."""
+@pytest.mark.parametrize("hd,G,S", [pytest.param(128, 4, 4097, id="128-4-None-4097"),  # ids: as test_one_pass
+                                    pytest.param(64, 1, 8193, id="64-1-1-8193")])
+def test_non_temporal_one_pass(hd, G, S, monkeypatch):
+    """ns = 7 (fast combine) and 13 (the loop combine kernel) from the capacity; the key loads keep the default
+    policy at G = 4 and are non-temporal, as the value loads, at G = 1."""
     B, Hkv = 2, 8
     ns = -(-S // 640)
     lens = (S - 1, S - 700)
     fx = ax.decode(B, G * Hkv, Hkv, hd, S, lens, ns, True, hd == 128, edges=(16, 128, 320))
-    for knt in (0, 1):
-        _one_pass(monkeypatch, rs=rs, knt=knt)
-        ws, _ = _run(fx, ws_splits=ns + 1, who=f"NT 1p KNT={knt}")
-        _assert_one_pass_ran(fx, ws, ns, ns + 1)
+    _one_pass(monkeypatch)
+    ws, _ = _run(fx, ws_splits=ns + 1, who="NT 1p")
+    _assert_one_pass_ran(fx, ws, ns, ns + 1)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -259,10 +258,10 @@ def test_repeated_launches_are_bit_identical(family, monkeypatch):
         fx = ax.decode(len(lens), 8, 2, 128, 300, lens, 9, True, True, edges=(16, 256))
         _batched(monkeypatch)
     else:
-        hd, G, rs = (128, 4, None) if family == "one_pass_mfma" else (64, 1, 1)
+        hd, G = (128, 4) if family == "one_pass_mfma" else (64, 1)  # GQA: MFMA scores; MHA: row-layout scores
         lens = _1p_lens(1300, True)
         fx = ax.decode(len(lens), G * 2, 2, hd, 1300, lens, 3, True, hd == 128, edges=(16, 128, 320))
-        _one_pass(monkeypatch, rs=rs)
+        _one_pass(monkeypatch)
         ws_splits = 3
     first = None
     for i in range(20):

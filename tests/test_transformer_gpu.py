@@ -161,24 +161,16 @@ def test_flash_attn_spike_rescale():
 
 
 def _decode_path(monkeypatch, path):
-    """'batched': the batched kernel everywhere; '1p': the one-pass kernel, forced onto grids of any size."""
-    if path in ("1p", "1p_rs", "1p_kf"):
-        monkeypatch.setenv("DNN_DECODE_1P", "2")
-        monkeypatch.setenv("DNN_DECODE_1P_RS", "1" if path == "1p_rs" else "0")
-        monkeypatch.setenv("DNN_DECODE_1P_KF", "1" if path == "1p_kf" else "0")
-    elif path == "1p_default":
-        monkeypatch.setenv("DNN_DECODE_1P", "2")
-        for k in ("DNN_DECODE_1P_RS", "DNN_DECODE_1P_KF", "DNN_DECODE_1P_KNT"):
-            monkeypatch.delenv(k, raising=False)
-    else:
-        monkeypatch.setenv("DNN_DECODE_1P", "0")
+    """'batched': the batched kernel everywhere; '1p': the one-pass kernel, forced onto grids of any size
+    ('1p_default': a second name of the same route, which only test_attn_decode_qkv_fused still uses)."""
+    monkeypatch.setenv("DNN_DECODE_1P", {"batched": "0", "1p": "2", "1p_default": "2"}[path])
 
 
 @pytest.mark.parametrize("B,H,Hkv,hd,S,lens", [(2, 12, 12, 64, 1024, [1, 700]), (3, 32, 8, 128, 2048, [5, 1000, 2048]),
                                                (1, 4, 2, 128, 300, [299]), (4, 25, 25, 64, 512, [17, 64, 65, 512]),
                                                (1, 32, 8, 128, 131072, [120001]),   # long context: LDS-bound splits
                                                (2, 12, 12, 64, 65536, [65536, 9000])])
-@pytest.mark.parametrize("path", ["batched", "1p", "1p_rs", "1p_kf", "1p_default"])
+@pytest.mark.parametrize("path", ["batched", "1p"])
 def test_attn_decode(B, H, Hkv, hd, S, lens, path, monkeypatch):
     """The batched decode kernel (DPP row reductions at MHA, MFMA key tiles at
     GQA) and the one-pass kernel (forced by DNN_DECODE_1P=2 on these small
@@ -683,7 +675,7 @@ def test_linear_norm_strided_rows():
     (1, 32, 8, 128, 200, [150], True, 1), (3, 12, 12, 64, 300, [0, 17, 299], False, 2),
     (2, 8, 2, 128, 1024, [700, 1023], True, 4), (2, 4, 4, 64, 64, [63, 64], False, 1),
     (1, 32, 8, 128, 600, [140], True, 1), (1, 32, 8, 128, 600, [599], True, 3)])
-@pytest.mark.parametrize("path", ["batched", "1p", "1p_rs", "1p_kf", "1p_default"])
+@pytest.mark.parametrize("path", ["batched", "1p", "1p_default"])
 def test_attn_decode_qkv_fused(B, H, Hkv, hd, S, pos, rope, splits, path, monkeypatch):
     """Fused decode step (split + RoPE + cache write + attention) == qkv_split
     then attn_decode, and the cache row it wrote matches; pos >= S (overflow)

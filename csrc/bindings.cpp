@@ -259,6 +259,28 @@ PYBIND11_MODULE(_dnn_hip, m) {
   }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("tok"), py::arg("pos"), py::arg("pos_off"),
      py::arg("n"), py::arg("lp_hist"), py::arg("top_id_hist"), py::arg("top_lp_hist"), py::arg("hist_ld"),
      py::arg("top_ld"), py::arg("ws"), py::arg("ws_rows"), py::arg("ws_ld"), py::arg("st"));
+  m.attr("STOP_STATE_WORDS") = DNN_STOP_STATE_WORDS;
+  m.def("stop_rows", [](u64 tok, u64 also, u64 hist, int hist_ld, u64 pos, int pos_off, u64 state,
+                        const std::vector<int>& stop_ids, const std::vector<std::vector<int>>& stop_seqs, int min_new,
+                        int pad, int M, u64 st) {
+    // the sequences as the [n][16] table of the C entry; an over-long one keeps its length, which the entry rejects
+    std::vector<int> flat(stop_seqs.size() * DNN_STOP_MAX_SEQ_LEN + 1, -1), lens(stop_seqs.size() + 1, 0);
+    for (size_t s = 0; s < stop_seqs.size(); ++s) {
+      lens[s] = (int)stop_seqs[s].size();
+      for (size_t j = 0; j < stop_seqs[s].size() && j < (size_t)DNN_STOP_MAX_SEQ_LEN; ++j)
+        flat[s * DNN_STOP_MAX_SEQ_LEN + j] = stop_seqs[s][j];
+    }
+    return dnn_stop_rows(IP(tok), IP(also), IP(hist), hist_ld, CIP(pos), pos_off, IP(state), stop_ids.data(),
+                         (int)stop_ids.size(), flat.data(), lens.data(), (int)stop_seqs.size(), min_new, pad, M,
+                         ST(st));
+  }, py::arg("tok"), py::arg("also"), py::arg("hist"), py::arg("hist_ld"), py::arg("pos"), py::arg("pos_off"),
+     py::arg("state"), py::arg("stop_ids"), py::arg("stop_seqs"), py::arg("min_new"), py::arg("pad"), py::arg("M"),
+     py::arg("st"));
+  m.def("stop_suppress", [](u64 x, int ld, int M, int N, u64 state, const std::vector<int>& stop_ids, int min_new,
+                            u64 st) {
+    return dnn_stop_suppress(P(x), ld, M, N, CIP(state), stop_ids.data(), (int)stop_ids.size(), min_new, ST(st));
+  }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("state"), py::arg("stop_ids"),
+     py::arg("min_new"), py::arg("st"));
   m.def("quant_fp8_rows", [](u64 x, int ldx, u64 q, u64 scale, int M, int K, int kpad, u64 st, int split) {
     return dnn_quant_fp8_rows(CP(x), ldx, P(q), FP(scale), M, K, kpad, ST(st), split);
   }, py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("scale"), py::arg("M"), py::arg("K"), py::arg("kpad"),

@@ -154,6 +154,26 @@ int dnn_logprobs_ws_row_words(int N, int n);
 int dnn_logprobs_rows(const void* x, int ld, int M, int N, const int* tok, const int* pos, int pos_off, int n,
                       float* lp_hist, int* top_id_hist, float* top_lp_hist, int hist_ld, int top_ld, void* ws,
                       int ws_rows, int ws_ld, hipStream_t st);
+// stop tokens / stop sequences / min_new_tokens (stop.hip, which states the semantics).  state: int32
+// [rows][DNN_STOP_STATE_WORDS] on the device = {g, finish length (0 = running), reason code (1 + id index,
+// 17 + sequence index), the last 15 generated tokens newest first}.  The tables are HOST arrays, copied into
+// the launch's arguments: stop_ids[n_ids], seqs[n_seq][DNN_STOP_MAX_SEQ_LEN] (oldest first, seq_len[s]
+// entries used).  dnn_stop_rows runs behind the argmax / sampler launch on its tokens tok[M]: a finished
+// row's token becomes pad in tok, also (optional) and hist[row * hist_ld + p] (optional; p = pos[row] +
+// pos_off, pos null: pos_off; p outside [0, hist_ld) writes nothing); a running row counts and matches it.
+// dnn_stop_suppress writes bf16 -inf into x[row, id] for every stop id of a running row with g < min_new.
+// -1, nothing launched: null tok / state / x, counts above the caps, a sequence length outside 1..16, a
+// negative id, pad or min_new, an id >= N (suppress), ld not a multiple of 8 or below N, x not 16-byte
+// aligned; -2: M > 2^24.  M <= 0 returns 0.
+#define DNN_STOP_STATE_WORDS 18
+#define DNN_STOP_MAX_IDS 16
+#define DNN_STOP_MAX_SEQS 8
+#define DNN_STOP_MAX_SEQ_LEN 16
+int dnn_stop_rows(int* tok, int* also, int* hist, int hist_ld, const int* pos, int pos_off, int* state,
+                  const int* stop_ids, int n_ids, const int* seqs, const int* seq_len, int n_seq, int min_new,
+                  int pad, int M, hipStream_t st);
+int dnn_stop_suppress(void* x, int ld, int M, int N, const int* state, const int* stop_ids, int n_ids, int min_new,
+                      hipStream_t st);
 int dnn_quant_fp8_rows(const void* x, int ldx, void* q, float* scale, int M, int K, int kpad, hipStream_t st,
                        int split = 0);
 int dnn_gemm_fp8(const void* A, const float* sa, const void* W, const float* sw, void* C, int ldc, const float* bias,

@@ -13,7 +13,8 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
   top level ``model``, ``dtype``, ``transport``, ``micro_batch_size``,
   ``num_microbatches``, ``seq_len``, ``decode_steps``, ``prompt_len``, ``temperature``, ``top_k``,
   ``top_p``, ``min_p``, ``seed``, ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``,
-  ``logprobs``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
+  ``logprobs``, ``eos_token_id``, ``stop_token_ids``, ``stop_sequences``, ``min_new_tokens``,
+  ``pad_token_id``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
   ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``input_dtype``, ``input_mean``,
   ``input_std`` (CIFAR: stage 0 takes uint8 images and normalises them by table); per node
   ``layers: [start, end]`` (inclusive, as in
@@ -60,6 +61,78 @@ class NodeSpec:
 LOGPROBS_MAX_N = 20
 
 
+# caps of the stop conditions: the tables of csrc/kernels/stop.hip are sized by them
+STOP_MAX_IDS = 16
+STOP_MAX_SEQS = 8
+STOP_MAX_SEQ_LEN = 16
+
+
+@dataclass(frozen=True)
+class StopConfig:
+    """The stop conditions of a generation (runtime/sampling.py ``stop_ref``
+    states the semantics): what a last stage gets when any is configured."""
+
+    stop_token_ids: Tuple[int, ...] = ()
+    stop_sequences: Tuple[Tuple[int, ...], ...] = ()
+    min_new_tokens: int = 0
+    pad_token_id: int = 0
+
+
+def _is_int(v: Any) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def make_stop(vocab: int, eos_token_id: Any = None, stop_token_ids: Any = None, stop_sequences: Any = None,
+              min_new_tokens: Any = 0, pad_token_id: Any = None) -> Optional[StopConfig]:
+    """Validate the five stop keys against a vocabulary of ``vocab`` entries.
+    ``eos_token_id`` (an int or a list of ints) is shorthand: its ids are
+    appended to ``stop_token_ids``.  Returns None when there is no stop id and
+    no stop sequence (the neutral case); raises ``ConfigError`` otherwise for a
+    value out of range, a duplicate, a count above the caps or a
+    ``min_new_tokens`` > 0 without anything to stop at."""
+    def ids_of(key: str, v: Any) -> List[int]:
+        if not isinstance(v, (list, tuple)) or any(not _is_int(e) for e in v):
+            raise ConfigError(f"ERROR: '{key}' must be a list of integers, got {v!r}")
+        bad = [e for e in v if not 0 <= e < vocab]
+        if bad:
+            raise ConfigError(f"ERROR: '{key}' holds ids outside [0, {vocab}): {bad!r}")
+        return [int(e) for e in v]
+
+    ids = ids_of("stop_token_ids", [] if stop_token_ids is None else stop_token_ids)
+    if eos_token_id is not None:
+        if isinstance(eos_token_id, bool) or not isinstance(eos_token_id, (int, list, tuple)):
+            raise ConfigError(f"ERROR: 'eos_token_id' must be an integer or a list of integers, got {eos_token_id!r}")
+        ids += ids_of("eos_token_id", [eos_token_id] if _is_int(eos_token_id) else eos_token_id)
+    if len(set(ids)) != len(ids):
+        raise ConfigError(f"ERROR: the stop ids ('stop_token_ids' and 'eos_token_id') must be distinct, got {ids!r}")
+    if len(ids) > STOP_MAX_IDS:
+        raise ConfigError(f"ERROR: at most {STOP_MAX_IDS} stop ids ('stop_token_ids' and 'eos_token_id'), got {len(ids)}")
+    seqs_in = [] if stop_sequences is None else stop_sequences
+    if not isinstance(seqs_in, (list, tuple)) or any(not isinstance(q, (list, tuple)) for q in seqs_in):
+        raise ConfigError(f"ERROR: 'stop_sequences' must be a list of lists of integers, got {stop_sequences!r}")
+    if len(seqs_in) > STOP_MAX_SEQS:
+        raise ConfigError(f"ERROR: at most {STOP_MAX_SEQS} 'stop_sequences', got {len(seqs_in)}")
+    seqs = []
+    for q in seqs_in:
+        if not 1 <= len(q) <= STOP_MAX_SEQ_LEN:
+            raise ConfigError(f"ERROR: every entry of 'stop_sequences' holds 1..{STOP_MAX_SEQ_LEN} ids, got {len(q)}")
+        seqs.append(tuple(ids_of("stop_sequences", q)))
+    if not _is_int(min_new_tokens) or min_new_tokens < 0:
+        raise ConfigError(f"ERROR: 'min_new_tokens' must be an integer >= 0, got {min_new_tokens!r}")
+    if pad_token_id is not None and (not _is_int(pad_token_id) or not 0 <= pad_token_id < vocab):
+        raise ConfigError(f"ERROR: 'pad_token_id' must be an id in [0, {vocab}), got {pad_token_id!r}")
+    if not ids and not seqs:
+        if min_new_tokens > 0:
+            raise ConfigError("ERROR: 'min_new_tokens' needs at least one stop id or stop sequence "
+                              "('eos_token_id', 'stop_token_ids', 'stop_sequences')")
+        return None
+    pad = int(pad_token_id) if pad_token_id is not None else (ids[0] if ids else 0)
+    return StopConfig(tuple(ids), tuple(seqs), int(min_new_tokens), pad)
+
+
+STOP_KEYS = ("eos_token_id", "stop_token_ids", "stop_sequences", "min_new_tokens", "pad_token_id")
+
+
 @dataclass
 class PipelineConfig:
     """The whole topology: every stage, in stage order."""
@@ -89,6 +162,7 @@ class PipelineConfig:
     presence_penalty: float = 0.0             # subtracted once from the logit of every generated token (0 = off)
     frequency_penalty: float = 0.0            # subtracted per time the token was generated (0 = off)
     logprobs: int = 0                         # 1..20: record each token's log-probability and the top-n (0 = off)
+    stop: Optional[StopConfig] = None         # stop ids / sequences, min_new_tokens, pad_token_id (None = never stops)
     rpc_timeout_s: Optional[float] = None     # per-hop SendTensor deadline (reference: none)
     health_timeout_s: float = 120.0           # readiness barrier before stage 0 sends
     comm_timeout_s: float = 300.0             # process-group (RCCL/gloo) op timeout
@@ -249,6 +323,14 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         raise ConfigError(f"ERROR: 'logprobs' must be an integer in [0, {LOGPROBS_MAX_N}], got {nlp!r}")
     if model == "cifar10" and nlp != 0:
         raise ConfigError(f"ERROR: 'logprobs' {nlp!r} exists for the generating models only, got model '{model}'")
+    stop = None
+    if any(cfg.get(k) is not None for k in STOP_KEYS):
+        if model == "cifar10":
+            raise ConfigError(f"ERROR: {[k for k in STOP_KEYS if cfg.get(k) is not None]!r} exist for the generating "
+                              f"models only, got model '{model}'")
+        from .models import model_info  # the vocabulary (imports torch: only when a stop key is present)
+        stop = make_stop(model_info(model).cfg.vocab_size, **{k: cfg.get(k) for k in STOP_KEYS if k != "min_new_tokens"},
+                         min_new_tokens=cfg.get("min_new_tokens", 0))
     if model == "cifar10":
         for key, v, neutral in (("repetition_penalty", rp, 1), ("presence_penalty", pens["presence_penalty"], 0),
                                 ("frequency_penalty", pens["frequency_penalty"], 0)):
@@ -283,7 +365,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         prefill_chunk=int(cfg.get("prefill_chunk", 0)),
         temperature=float(cfg.get("temperature", 0.0)), top_k=int(cfg.get("top_k", 0)), seed=int(cfg.get("seed", 0)),
         top_p=float(tp), min_p=float(mp), repetition_penalty=float(rp), presence_penalty=pens["presence_penalty"],
-        frequency_penalty=pens["frequency_penalty"], logprobs=nlp,
+        frequency_penalty=pens["frequency_penalty"], logprobs=nlp, stop=stop,
         rpc_timeout_s=cfg.get("rpc_timeout_s"), health_timeout_s=float(cfg.get("health_timeout_s", 120.0)),
         comm_timeout_s=float(cfg.get("comm_timeout_s", 300.0)),
         heartbeat_timeout_s=float(cfg.get("heartbeat_timeout_s", 15.0)),

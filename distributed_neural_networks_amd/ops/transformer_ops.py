@@ -8,7 +8,9 @@ from typing import Optional
 
 import torch
 
-from ..config import LOGPROBS_MAX_N
+from ..config import LOGPROBS_MAX_N, STOP_MAX_IDS, STOP_MAX_SEQ_LEN, STOP_MAX_SEQS
+
+STOP_STATE_WORDS = 18  # csrc/kernels/api.h DNN_STOP_STATE_WORDS
 from ._lib import check, lib, ptr, stream_ptr
 
 
@@ -426,3 +428,86 @@ def logprobs_rows(logits: torch.Tensor, tokens: torch.Tensor, n_vocab: int, n: i
                               pos_off=int(pos_off), n=n, lp_hist=ptr(chosen), top_id_hist=ptr(top_ids if n else None),
                               top_lp_hist=ptr(top_lps if n else None), hist_ld=L, top_ld=top_ld, ws=ptr(ws),
                               ws_rows=ws.shape[0], ws_ld=ws.shape[1], st=stream_ptr()), "logprobs_rows")
+
+
+def stop_state(rows: int, device) -> torch.Tensor:
+    """The stop state of ``rows`` KV-cache rows at the beginning of a generation
+    (stop.hip): int32 (rows, 18) = g, finish length, reason code and the
+    15-entry window, the window all -1."""
+    st = torch.zeros((int(rows), STOP_STATE_WORDS), dtype=torch.int32, device=device)
+    st[:, 3:] = -1
+    return st
+
+
+def _stop_tables(stop_ids, stop_seqs, who: str):
+    ids = [int(i) for i in stop_ids]
+    seqs = [[int(e) for e in s] for s in stop_seqs]
+    if len(ids) > STOP_MAX_IDS or len(seqs) > STOP_MAX_SEQS:
+        raise ValueError(f"{who}: at most {STOP_MAX_IDS} stop ids and {STOP_MAX_SEQS} stop sequences, got {len(ids)} "
+                         f"and {len(seqs)}")
+    if any(not 1 <= len(s) <= STOP_MAX_SEQ_LEN for s in seqs):
+        raise ValueError(f"{who}: a stop sequence holds 1..{STOP_MAX_SEQ_LEN} ids")
+    if any(i < 0 for i in ids) or any(e < 0 for s in seqs for e in s):
+        raise ValueError(f"{who}: negative id")
+    return ids, seqs
+
+
+def stop_rows(tokens: torch.Tensor, state: torch.Tensor, stop_ids, stop_seqs, min_new: int, pad: int,
+              also: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
+              pos: Optional[torch.Tensor] = None, pos_off: int = 0) -> None:
+    """The stop launch of one step (stop.hip; ``runtime/sampling.stop_ref`` is
+    the mirror and states the semantics) on the M tokens the argmax / sampler
+    launch just wrote to ``tokens`` (int32).  A row of ``state`` (int32 (>= M,
+    18), ``stop_state``) that has finished gets ``pad`` in ``tokens``, in
+    ``also`` (the next input ids, when given) and in ``hist[row, p]`` (the token
+    history, when given) with ``p = pos[row] + pos_off`` (``pos`` None:
+    ``pos_off``; ``pos_off = -1`` when the step tail has advanced ``pos``
+    already; ``p`` outside the history writes nothing).  A running row counts
+    its token, pushes it into its window and finishes on a stop id or a stop
+    sequence."""
+    M = tokens.numel()
+    ids, seqs = _stop_tables(stop_ids, stop_seqs, "stop_rows")
+    if int(min_new) < 0 or int(pad) < 0:
+        raise ValueError(f"stop_rows: min_new {min_new!r} and pad {pad!r} must be >= 0")
+    for t, nm in ((tokens, "tokens"), (also, "also"), (pos, "pos")):
+        if t is not None and (t.dtype != torch.int32 or t.numel() < M or not t.is_contiguous()):
+            raise ValueError(f"stop_rows: {nm} must be contiguous int32 with >= {M} entries")
+    if (state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != STOP_STATE_WORDS or state.shape[0] < M
+            or not state.is_contiguous()):
+        raise ValueError(f"stop_rows: state must be contiguous int32 (>= {M}, {STOP_STATE_WORDS}), got {state.dtype} "
+                         f"{tuple(state.shape)}")
+    hist_ld = 0
+    if hist is not None:
+        if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] < M or hist.stride(1) != 1:
+            raise ValueError(f"stop_rows: hist must be int32 (>= {M}, L) with contiguous rows")
+        hist_ld = hist.stride(0) if hist.shape[0] > 1 else hist.shape[1]
+        if hist_ld < hist.shape[1]:
+            raise ValueError("stop_rows: overlapping hist rows")
+    check(lib().stop_rows(tok=ptr(tokens), also=ptr(also), hist=ptr(hist), hist_ld=hist_ld, pos=ptr(pos),
+                          pos_off=int(pos_off), state=ptr(state), stop_ids=ids, stop_seqs=seqs, min_new=int(min_new),
+                          pad=int(pad), M=M, st=stream_ptr()), "stop_rows")
+
+
+def stop_suppress(logits: torch.Tensor, n_vocab: int, state: torch.Tensor, stop_ids, min_new: int) -> torch.Tensor:
+    """bf16 -inf in place at every stop id of each row of ``logits`` (M, >=
+    n_vocab) whose ``state`` row is running with fewer than ``min_new`` tokens
+    generated (stop.hip; mirror ``runtime/sampling.stop_suppress_ref``)."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("stop_suppress: bf16 (M, >= n_vocab) logits with contiguous rows expected")
+    M = logits.shape[0]
+    if not 0 < n_vocab <= logits.shape[1]:
+        raise ValueError(f"stop_suppress: n_vocab = {n_vocab} outside the row width {logits.shape[1]}")
+    ids, _ = _stop_tables(stop_ids, (), "stop_suppress")
+    if any(i >= n_vocab for i in ids):
+        raise ValueError(f"stop_suppress: stop id outside [0, {n_vocab})")
+    if int(min_new) < 0:
+        raise ValueError(f"stop_suppress: min_new {min_new!r} must be >= 0")
+    ld = logits.stride(0) if M > 1 else logits.shape[1]
+    if ld % 8 or ld < n_vocab or logits.data_ptr() % 16:
+        raise ValueError("stop_suppress: rows must start 16-byte aligned (row stride a multiple of 8, >= n_vocab)")
+    if (state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != STOP_STATE_WORDS or state.shape[0] < M
+            or not state.is_contiguous()):
+        raise ValueError(f"stop_suppress: state must be contiguous int32 (>= {M}, {STOP_STATE_WORDS})")
+    check(lib().stop_suppress(x=ptr(logits), ld=ld, M=M, N=int(n_vocab), state=ptr(state), stop_ids=ids,
+                              min_new=int(min_new), st=stream_ptr()), "stop_suppress")
+    return logits

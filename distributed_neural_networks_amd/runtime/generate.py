@@ -109,19 +109,34 @@ def _report_logprobs(nid: str, ring: DecodeRing) -> None:
     log("LOGPROBS " + json.dumps(rec))
 
 
+def _report_finish(nid: str, ring: DecodeRing) -> None:
+    """One ``FINISH {...}`` JSON line from the rank that holds the last stage
+    (config keys ``eos_token_id`` / ``stop_token_ids`` / ``stop_sequences``):
+    every sequence's number of valid tokens in the ``generated tokens`` line
+    (the rest of its row is ``pad_token_id``) and why it ended: null (it never
+    stopped), ``["token", index]`` or ``["sequence", index]``."""
+    if ring.stp is None:
+        return
+    fin = ring.finished()
+    log("FINISH " + json.dumps({"node": nid, "pad_token_id": ring.stp.stop.pad_token_id,
+                                "length": fin["length"].tolist(),
+                                "reason": [None if r is None else list(r) for r in fin["reason"]]}))
+
+
 def _timed_generate(ring: DecodeRing, prompts, T: int, steps: int, dev, chunk: int = 0):
+    """(prefill seconds, decode seconds, tokens per sequence): the last is
+    ``steps`` unless the ring left early because every sequence had stopped."""
     t0 = time.perf_counter()
     ring.prefill(prompts, T, chunk)
     if steps > 1:
         ring.capture()
     _sync(dev)
     t1 = time.perf_counter()
-    if steps > 1:
-        ring.decode_rounds(steps - 1)
+    ran = ring.decode_rounds(steps - 1) if steps > 1 else 0
     ring.drain()
     _sync(dev)
     t2 = time.perf_counter()
-    return t1 - t0, t2 - t1
+    return t1 - t0, t2 - t1, 1 + ran
 
 
 def run_generate_colocated(ctx, args, stages: List, device) -> int:
@@ -133,9 +148,10 @@ def run_generate_colocated(ctx, args, stages: List, device) -> int:
     M, B = pipe.num_microbatches, pipe.micro_batch_size
     ring = DecodeRing(stages, RingLinks(), 1, M, B)
     prompts = [prompt[m * B:(m + 1) * B] for m in range(M)]
-    pf, dec = _timed_generate(ring, prompts, T, steps, device, pipe.prefill_chunk)
+    pf, dec, steps = _timed_generate(ring, prompts, T, steps, device, pipe.prefill_chunk)
     _report(ctx.node_id, ring.tokens(), pf, dec, n_seq, T, steps, M, 1)
     _report_logprobs(ctx.node_id, ring)
+    _report_finish(ctx.node_id, ring)
     return 0
 
 
@@ -169,9 +185,10 @@ def run_generate_dist(ctx, args, stage, info, progress=None) -> int:
         links.nxt.send_header(KIND_DATA, B, T, steps)
     check_capacity([stage], *kv_capacity(pipe, T))
     ring = DecodeRing([stage], links, S, M, B, progress=progress, forward_prompt_ids=penalties_on(pipe))
-    pf, dec = _timed_generate(ring, prompts, T, steps, dev, pipe.prefill_chunk)
+    pf, dec, steps = _timed_generate(ring, prompts, T, steps, dev, pipe.prefill_chunk)
     if r == 0:
         nid = ctx.node_id + (f" replica {ctx.replica}" if getattr(pipe, "replicas", 1) > 1 else "")
         _report(nid, ring.tokens(), pf, dec, B * M, T, steps, M, S)
     _report_logprobs(ctx.node_id, ring)  # the last rank's: nothing new travels over the back-edge
+    _report_finish(ctx.node_id, ring)  # likewise: the padded tokens are all that travels
     return 0

@@ -20,7 +20,7 @@ from typing import Optional
 
 import torch
 
-from ..config import LOGPROBS_MAX_N
+from ..config import LOGPROBS_MAX_N, STOP_MAX_IDS, STOP_MAX_SEQ_LEN
 
 _M32 = 0xFFFFFFFF
 
@@ -212,6 +212,99 @@ def logprobs_ref(logits: torch.Tensor, tokens: torch.Tensor, n: int):
     chosen = lp.gather(1, tok[:, None])[:, 0].to(torch.float32)
     order = torch.sort(_keys(xb), dim=1, descending=True, stable=True).indices[:, :n]
     return chosen, order.to(torch.int32), lp.gather(1, order).to(torch.float32)
+
+
+# ---------------------------------------------------------------------- stop conditions
+STOP_STATE_WORDS = 18  # csrc/kernels/api.h DNN_STOP_STATE_WORDS: g, finish length, reason code, 15 window entries
+_STOP_WIN = STOP_STATE_WORDS - 3
+
+
+def stop_state(rows: int, device="cpu") -> torch.Tensor:
+    """The stop state of ``rows`` sequences at the beginning of a generation:
+    int32 (rows, 18) = ``[g, finish length, reason code, window[0..15)]`` with
+    nothing generated, nothing finished and the window all -1."""
+    st = torch.zeros((rows, STOP_STATE_WORDS), dtype=torch.int32, device=device)
+    st[:, 3:] = -1
+    return st
+
+
+def stop_reason(code: int):
+    """A state's reason code as ``None`` (running), ``("token", index)`` or
+    ``("sequence", index)``; the index is the one in the stage's list."""
+    code = int(code)
+    if code == 0:
+        return None
+    return ("token", code - 1) if code <= STOP_MAX_IDS else ("sequence", code - 1 - STOP_MAX_IDS)
+
+
+def stop_ref(state: torch.Tensor, tokens: torch.Tensor, stop_ids, stop_seqs, min_new: int, pad: int):
+    """One step of the stop conditions on host tensors: the torch mirror of
+    ``dnn_stop_rows`` (csrc/kernels/stop.hip) and the one written definition.
+
+    Per sequence, generated tokens count from 1: the token sampled from the
+    prompt's last position is token 1.  ``g`` = tokens generated before this
+    step.
+
+    1. Suppression (``min_new > 0`` only, ``stop_suppress_ref``): while
+       ``g < min_new`` every stop id's logit is bf16 -inf, after the penalties
+       and before the argmax / sampler.  A finished row is left alone.
+    2. The unchanged argmax / sampler picks token ``t``.
+    3. This function, last in the step, per row:
+       * finished already: ``t`` is replaced by ``pad``; the finish record does
+         not change.
+       * running: ``g += 1`` and ``t`` enters the row's window of the last 15
+         generated tokens.  The row finishes with length ``g`` when ``t`` is a
+         stop id (reason code 1 + index), else when the last ``len(s)``
+         generated tokens equal stop sequence ``s`` and
+         ``g >= max(min_new, len(s))`` (reason code 17 + index).  A stop id wins
+         over a sequence, the lowest index wins within a kind.  The stop token
+         or sequence stays in the output.  Prompt tokens never take part in a
+         match (``g >= len(s)``: every compared token was generated; the
+         window starts as -1).
+
+    ``state`` int32 (M, 18) as ``stop_state`` lays it out (window newest
+    first), ``tokens`` (M,) int.  Returns ``(new state, padded tokens int32)``;
+    neither argument is changed."""
+    st = state.detach().to(device="cpu", dtype=torch.int32).clone()
+    M = st.shape[0]
+    t = tokens.detach().to(device="cpu", dtype=torch.int32).reshape(M)
+    if st.shape[1] != STOP_STATE_WORDS:
+        raise ValueError(f"stop_ref: state (M, {STOP_STATE_WORDS}) expected, got {tuple(st.shape)}")
+    fin = st[:, 1] != 0
+    g1 = st[:, 0] + 1
+    h = torch.cat([t[:, None], st[:, 3:]], 1)  # the last 16 generated tokens, newest first
+    reason = torch.zeros((M,), dtype=torch.int32)
+    for k in reversed(range(len(stop_seqs))):  # lower indices overwrite higher ones
+        s = [int(e) for e in stop_seqs[k]]
+        L = len(s)
+        if not 1 <= L <= STOP_MAX_SEQ_LEN:
+            raise ValueError(f"stop_ref: sequence length {L} outside 1..{STOP_MAX_SEQ_LEN}")
+        hit = (h[:, :L] == torch.tensor(s[::-1], dtype=torch.int32)).all(1) & (g1 >= max(int(min_new), L))
+        reason = torch.where(hit, torch.tensor(1 + STOP_MAX_IDS + k, dtype=torch.int32), reason)
+    for k in reversed(range(len(stop_ids))):  # ... and a stop id overwrites every sequence
+        reason = torch.where(t == int(stop_ids[k]), torch.tensor(1 + k, dtype=torch.int32), reason)
+    run = ~fin
+    new = st.clone()
+    new[:, 0] = torch.where(run, g1, st[:, 0])
+    new[:, 1] = torch.where(run & (reason != 0), g1, st[:, 1])
+    new[:, 2] = torch.where(run, reason, st[:, 2])
+    new[:, 3:] = torch.where(run[:, None], h[:, :_STOP_WIN], st[:, 3:])
+    return new, torch.where(fin, torch.tensor(int(pad), dtype=torch.int32), t)
+
+
+def stop_suppress_ref(logits: torch.Tensor, state: torch.Tensor, stop_ids, min_new: int) -> torch.Tensor:
+    """Mirror of ``dnn_stop_suppress``: a copy of the (M, N) ``logits`` with -inf
+    at every stop id of each row that is running and has generated fewer than
+    ``min_new`` tokens."""
+    x = logits.clone()
+    if int(min_new) <= 0 or len(stop_ids) == 0:
+        return x
+    st = state.to(device=x.device)
+    rows = (st[: x.shape[0], 1] == 0) & (st[: x.shape[0], 0] < int(min_new))
+    ids = torch.tensor([int(i) for i in stop_ids], dtype=torch.int64, device=x.device)
+    sub = x[:, ids]
+    x[:, ids] = torch.where(rows[:, None], torch.full_like(sub, float("-inf")), sub)
+    return x
 
 
 def pick(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0,

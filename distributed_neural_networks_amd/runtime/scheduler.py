@@ -306,8 +306,12 @@ class DecodeRing:
 
     def __init__(self, stages: Sequence, links: RingLinks, n_groups: int, M: int, B: int,
                  use_graphs: bool = True, record: bool = True, progress: Progress = None, lanes: int = 0,
-                 multi_step: int = -1, forward_prompt_ids: bool = False):
-        """``forward_prompt_ids`` (more than one group; every rank passes the
+                 multi_step: int = -1, forward_prompt_ids: bool = False, early_exit: bool = True):
+        """``early_exit`` (one group, a last stage with stop conditions):
+        ``decode_rounds`` returns once every row of every microbatch has
+        finished (checked every K rounds, one check behind: see there).
+
+        ``forward_prompt_ids`` (more than one group; every rank passes the
         same value, it follows the config): a last stage with penalties
         (``penalties_on``) needs the prompt's token ids, which only group 0
         has, so before a microbatch's first prefill piece rank 0 sends its
@@ -421,6 +425,15 @@ class DecodeRing:
             self.lp_top_lps = [torch.zeros((B, cap, self.lp_n), dtype=torch.float32, device=dev) for _ in range(M)]
             for m in range(M):
                 self.stages[-1].bind_logprobs(m * B, self.lp_chosen[m], self.lp_top_ids[m], self.lp_top_lps[m])
+
+        # last stage with stop conditions (its ``stop`` is a config.StopConfig): the per-row state lives on the
+        # stage, starts at every prefill (stop_begin), forgets the discarded sample of a non-final prefill
+        # piece (stop_forget) and survives the capture runs through snapshots (capture)
+        self.stp = self.stages[-1] if self.last and getattr(self.stages[-1], "stop", None) is not None else None
+        self.n_gen = [0] * M  # tokens generated per sequence of microbatch m in the current generation (last rank)
+        self.early_exit = bool(early_exit) and n_groups == 1 and self.stp is not None
+        self._fin_host = self._fin_ev = None  # pinned copies of the stop state and their events (GPU)
+        self._fin_i = 0  # checks queued in the current generation
 
     # -- one microbatch through this rank's stages --------------------------
     def _run(self, x, m: int, T: int, out=None, advance=None):
@@ -551,6 +564,9 @@ class DecodeRing:
                 self.links.prev.recv(ids)
             if self.forward_prompt_ids and not self.last:
                 id_work.append((self.links.nxt.isend(ids), ids))
+            if self.stp is not None:
+                self.stp.stop_begin(m * B, B)
+                self.n_gen[m] = 0
             if self.pen is not None:
                 # the whole prompt is marked before its first token is sampled (chunked prefill and the
                 # fp8-KV calibration prefills included: each starts from the prompt alone)
@@ -571,10 +587,13 @@ class DecodeRing:
                 self.pos[m].add_(Tc)
                 if self.pen is not None and not final:
                     self.pen.penalty_forget(m * B, B)  # this piece's sample is discarded, never counted
+                if self.stp is not None and not final:
+                    self.stp.stop_forget(m * B, B)  # ... and neither counted nor matched as a generated token
                 if not self.last:
                     pf_work[k] = self.links.nxt.isend(out_pf[k][:B * Tc])
                     n_sent += 1
                 elif final:
+                    self.n_gen[m] = 1
                     if self.lp_chosen is not None:
                         self.lp_base[m], self.lp_cnt[m] = T - 1, 1  # the prompt's last position gave the first token
                     if self.G == 1:
@@ -593,6 +612,7 @@ class DecodeRing:
         if self.first and self.G > 1:
             self.pending = [True] * self.M  # every prompt's first token comes back over the back-edge
         self.steps_done = 0
+        self._fin_i = 0
 
     # -- decode -------------------------------------------------------------------
     def capture(self) -> None:
@@ -604,6 +624,7 @@ class DecodeRing:
             snap = self.pos[m].clone()
             cur = self.cur[m].clone() if self.first else None
             pen = self.pen.penalty_snapshot(m * self.B, self.B) if self.pen is not None else None
+            stp = self.stp.stop_snapshot(m * self.B, self.B) if self.stp is not None else None
             self._out_ready(m)
             self.graphs[m] = GraphedStep(lambda m=m: self._decode_body(m), self.dev, warmup=1)
             self.pos[m].copy_(snap)  # the warmup/capture runs advanced the position
@@ -611,6 +632,8 @@ class DecodeRing:
                 self.cur[m].copy_(cur)
             if pen is not None:
                 self.pen.penalty_restore(pen)  # ... counted their tokens and overwrote the previous-token entries
+            if stp is not None:
+                self.stp.stop_restore(stp)  # ... counted and matched them (a row may even have finished)
         torch.cuda.synchronize(self.dev)
         self._capture_multi_step()
 
@@ -628,6 +651,8 @@ class DecodeRing:
         cur = [c.clone() for c in self.cur] if self.first else None
         pen = ([self.pen.penalty_snapshot(m * self.B, self.B) for m in range(self.M)]
                if self.pen is not None else None)
+        stp = ([self.stp.stop_snapshot(m * self.B, self.B) for m in range(self.M)]
+               if self.stp is not None else None)
 
         def body():
             for _ in range(K):
@@ -641,6 +666,8 @@ class DecodeRing:
                     self.cur[m].copy_(cur[m])
                 if pen is not None:
                     self.pen.penalty_restore(pen[m])
+                if stp is not None:
+                    self.stp.stop_restore(stp[m])
         self.graph_k = GraphedStep(body, self.dev, warmup=1, reset=reset)
         self.graph_k_steps = K
         reset()  # the capture run advanced them again
@@ -653,8 +680,37 @@ class DecodeRing:
         one trip around the ring (per-token latency)."""
         self.decode_rounds(1, mbs)
 
-    def decode_rounds(self, n: int, mbs: Optional[Sequence[int]] = None) -> None:
-        """``n`` decode rounds.  The input of the next microbatch in the
+    def _all_finished(self) -> bool:
+        """Early exit: has every row of every microbatch finished?  On a GPU the
+        answer is one check old, so the queue never drains: the last stage's
+        stop state is copied to pinned host memory behind the work queued so
+        far and an event recorded; the host then waits for the event of the
+        PREVIOUS check only (the rounds queued since keep the device busy) and
+        reads that copy.  The ring therefore stops at most two check intervals
+        after the last row finished; the surplus tokens are pad tokens, so the
+        result does not depend on when the host noticed."""
+        n = self.M * self.B
+        st = self.stp.stop_state
+        if self.dev.type != "cuda":
+            return bool((st[:n, 1] != 0).all())
+        if self._fin_host is None:
+            self._fin_host = [torch.empty((n, st.shape[1]), dtype=torch.int32).pin_memory() for _ in range(2)]
+            self._fin_ev = [torch.cuda.Event() for _ in range(2)]
+        i = self._fin_i
+        self._fin_host[i & 1].copy_(st[:n], non_blocking=True)
+        self._fin_ev[i & 1].record()
+        self._fin_i = i + 1
+        if i == 0:
+            return False
+        self._fin_ev[(i - 1) & 1].synchronize()
+        return bool((self._fin_host[(i - 1) & 1][:, 1] != 0).all())
+
+    def decode_rounds(self, n: int, mbs: Optional[Sequence[int]] = None) -> int:
+        """``n`` decode rounds; returns the number it ran, which is ``n`` unless
+        ``early_exit`` (one group, stop conditions on the last stage, ``mbs``
+        None, no lanes) found every row finished: it looks after every K-step
+        replay, and every K = ``multi_step`` (or 8) rounds of the single-step
+        path (``_all_finished``).  The input of the next microbatch in the
         sequence (across round boundaries too, up to the last one of the
         ``n`` rounds) is received into its own slot while this one computes:
         its receive is posted *before* this microbatch's graph is launched
@@ -665,7 +721,10 @@ class DecodeRing:
         if self.lanes and mbs is None:
             for _ in range(n):
                 self._decode_round_lanes()
-            return
+            return n
+        total = n
+        early = self.early_exit and mbs is None
+        every = self.multi_step if self.multi_step >= 2 else 8  # rounds between two looks of the single-step path
         if self.graph_k is not None and mbs is None:
             K = self.graph_k_steps
             while n >= K and self.multi_step >= K:
@@ -675,10 +734,13 @@ class DecodeRing:
                 for m in range(self.M):
                     self.hist_n[m] += K
                     self.lp_cnt[m] += K
+                    self.n_gen[m] += K
                 self.progress()
                 n -= K
+                if early and n > 0 and self._all_finished():
+                    return total - n
             if n == 0:
-                return
+                return total
         order = list(range(self.M) if mbs is None else mbs)
         seq = [m for _ in range(n) for m in order]
         G = self.G
@@ -699,6 +761,7 @@ class DecodeRing:
                 else:
                     self._decode_body(m)
             self.lp_cnt[m] += 1
+            self.n_gen[m] += 1
             self._send(m)
             if self.first and G > 1:
                 self.pending[m] = True
@@ -706,7 +769,12 @@ class DecodeRing:
                 self._record_step(m)
             if i + 1 == len(seq) or (i + 1) % len(order) == 0:
                 self.steps_done += 1
+                rounds = (i + 1) // len(order)
+                if early and i + 1 < len(seq) and rounds % every == 0 and self._all_finished():
+                    self.progress()
+                    return total - n + rounds
             self.progress()
+        return total
 
     def _decode_round_lanes(self) -> None:
         """One group, M microbatches on ``len(self.lanes)`` streams: the round
@@ -725,6 +793,7 @@ class DecodeRing:
                         self._decode_body(m)
                 if self.record:
                     self._record_step(m)
+            self.n_gen[m] += 1
             self.progress()
         for s in self.lanes:
             cur.wait_stream(s)
@@ -747,7 +816,11 @@ class DecodeRing:
 
     def generate(self, prompts, T: int, steps: int, chunk: int = 0) -> Optional[torch.Tensor]:
         """Prefill + ``steps - 1`` decode rounds (``steps`` tokens per sequence).
-        Group 0 returns (M*B, steps) int32 on the host; other groups None."""
+        Group 0 returns (M*B, steps) int32 on the host; other groups None.
+        With stop conditions the columns past a row's length (``finished()``)
+        hold ``pad_token_id``, and with ``early_exit`` the result is
+        (M*B, steps_run), steps_run <= steps: the ring stopped once every row
+        had finished."""
         self.prefill(prompts, T, chunk)
         if steps > 1:
             self.capture()
@@ -773,6 +846,25 @@ class DecodeRing:
             rows.append(torch.cat(parts, 1))
         return torch.cat(rows, 0).cpu()
 
+    def finished(self) -> Dict[str, object]:
+        """The finish record of the current generation, on the rank that holds
+        the last stage (only that rank can answer, as with ``logprobs()``):
+        ``length`` int32 (M*B,), the number of valid tokens of each row (the
+        stop token or sequence included), or the number of tokens generated so
+        far when the row never stopped; ``reason``, per row ``None``,
+        ``("token", index)`` or ``("sequence", index)`` with the index into the
+        config's stop ids (``stop_token_ids`` then ``eos_token_id``) or stop
+        sequences."""
+        if self.stp is None:
+            raise ValueError("finished(): this rank's last stage has no stop conditions (config keys 'eos_token_id', "
+                             "'stop_token_ids', 'stop_sequences'; last group only)")
+        from .sampling import stop_reason
+        n = self.M * self.B
+        st = self.stp.stop_state[:n].cpu()
+        steps = torch.tensor(self.n_gen, dtype=torch.int32).repeat_interleave(self.B)
+        length = torch.where(st[:, 1] != 0, st[:, 1], steps)
+        return {"length": length.to(torch.int32), "reason": [stop_reason(c) for c in st[:, 2].tolist()]}
+
     def logprobs(self) -> Dict[str, torch.Tensor]:
         """The log-probabilities of the current generation, on the host and
         aligned with ``tokens()`` (column j belongs to the j-th generated
@@ -782,7 +874,10 @@ class DecodeRing:
         ``top_lps`` (M*B, steps, n) fp32, the n most likely entries by (value
         descending, index ascending).  Valid on the rank that holds the last
         stage (with one group: this process); nothing travels over the
-        back-edge."""
+        back-edge.  With stop conditions the columns past a row's length
+        (``finished()``) are unspecified: they belong to tokens that the stop
+        launch replaced by the pad token after the log-probability launch had
+        seen them."""
         if self.lp_chosen is None:
             raise ValueError("logprobs(): this rank's last stage records none (config key 'logprobs', last group only)")
         out = {"chosen": [], "top_ids": [], "top_lps": []}

@@ -166,21 +166,25 @@ class TorchStage(StageCompute):
     def __init__(self, model: str, sd: Dict[str, torch.Tensor], start: int, end: int, first: bool, last: bool,
                  device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0), input_dtype: str = "fp32", input_table=None):
         from ..models import build_golden_stage
-        # sampling = (temperature, top_k, seed[, top_p, min_p[, repetition, presence, frequency penalty[, logprobs]]])
-        if len(sampling) not in (3, 5, 8, 9):
-            raise ValueError(f"sampling: 3, 5, 8 or 9 entries expected, got {len(sampling)}")
+        # sampling = (temperature, top_k, seed[, top_p, min_p[, repetition, presence, frequency penalty[, logprobs
+        #             [, stop (config.StopConfig or None)]]]])
+        if len(sampling) not in (3, 5, 8, 9, 10):
+            raise ValueError(f"sampling: 3, 5, 8, 9 or 10 entries expected, got {len(sampling)}")
         self.temperature, self.top_k, self.seed = float(sampling[0]), int(sampling[1]), int(sampling[2])
         self.top_p, self.min_p = (float(sampling[3]), float(sampling[4])) if len(sampling) >= 5 else (1.0, 0.0)
         self.rep_pen, self.pres_pen, self.freq_pen = ((float(sampling[5]), float(sampling[6]), float(sampling[7]))
                                                       if len(sampling) >= 8 else (1.0, 0.0, 0.0))
         # log-probabilities (last stage): every last_only step records its token's and the top-n through
         # the mirror (runtime/sampling.py logprobs_ref) into the histories bound to its cache rows
-        nlp = sampling[8] if len(sampling) == 9 else 0
+        nlp = sampling[8] if len(sampling) >= 9 else 0
         from ..config import LOGPROBS_MAX_N
         if not isinstance(nlp, int) or isinstance(nlp, bool) or not 0 <= nlp <= LOGPROBS_MAX_N:
             raise ValueError(f"logprobs must be an integer in [0, {LOGPROBS_MAX_N}], got {nlp!r}")
         self.logprobs = nlp if last else 0
         self._lp_hist: Dict[int, tuple] = {}
+        # stop conditions (last stage): the mirror's state (runtime/sampling.py stop_ref) per microbatch offset
+        self.stop = sampling[9] if len(sampling) == 10 and last else None
+        self._stop_st: Dict[int, torch.Tensor] = {}
         import math
         if not (self.rep_pen > 0 and math.isfinite(self.rep_pen)):
             raise ValueError(f"repetition penalty must be a finite number > 0, got {sampling[5]!r}")
@@ -257,6 +261,35 @@ class TorchStage(StageCompute):
         """The sample of a prefill piece before the last one is no generated token."""
         self._pen_prev[b0] = None
 
+    def stop_begin(self, b0: int, B: int) -> None:
+        """Start a generation on cache rows [b0, b0 + B) (``TransformerStage.stop_begin``)."""
+        from .sampling import stop_state
+        if self.stop is None:
+            raise ValueError("stop_begin: this stage has no stop conditions")
+        self._stop_st[b0] = stop_state(B)
+
+    def stop_forget(self, b0: int, B: int) -> None:
+        """The sample of a prefill piece before the last one is neither counted nor matched."""
+        self.stop_begin(b0, B)
+
+    def stop_snapshot(self, b0: int, B: int):
+        return b0, B, self._stop_st[b0].clone()
+
+    def stop_restore(self, snap) -> None:
+        self._stop_st[snap[0]] = snap[2].clone()
+
+    @property
+    def stop_state(self) -> Optional[torch.Tensor]:
+        """The stop state of every begun row, in cache-row order (None: no stop conditions)."""
+        if self.stop is None:
+            return None
+        from .sampling import stop_state
+        n = max((b0 + st.shape[0] for b0, st in self._stop_st.items()), default=0)
+        out = stop_state(n)
+        for b0, st in self._stop_st.items():
+            out[b0:b0 + st.shape[0]] = st
+        return out
+
     def bind_logprobs(self, b0: int, chosen: torch.Tensor, top_ids: torch.Tensor, top_lps: torch.Tensor) -> None:
         """The histories of cache rows [b0, b0 + B) (``TransformerStage.bind_logprobs``):
         fp32 (B, L), int32 (B, L, n), fp32 (B, L, n); a ``last_only`` step writes
@@ -303,6 +336,15 @@ class TorchStage(StageCompute):
                     self._pen[b0] = penalty_count(self._pen[b0], self._pen_prev[b0])
                 logits = apply_penalties_ref(logits, self._pen[b0], self.rep_pen, self.freq_pen, self.pres_pen)
                 y = logits[:, None, :]
+            stp = self.stop is not None and last_only
+            if stp:
+                from .sampling import stop_ref, stop_suppress_ref
+                if b0 not in self._stop_st or self._stop_st[b0].shape[0] != B:
+                    raise ValueError(f"stop: no stop_begin for the {B} cache rows at {b0}")
+                if self.stop.min_new_tokens > 0 and self.stop.stop_token_ids:
+                    logits = stop_suppress_ref(logits, self._stop_st[b0], self.stop.stop_token_ids,
+                                               self.stop.min_new_tokens)
+                    y = logits[:, None, :]
             pred = pick(y[:, -1, :], self.temperature, self.top_k, self.seed, step, top_p=self.top_p,
                         min_p=self.min_p).to(torch.int32)
             if self.penalties_on and last_only:
@@ -318,6 +360,10 @@ class TorchStage(StageCompute):
                     chosen[:B, q] = c
                     top_ids[:B, q, :self.logprobs] = ti
                     top_lps[:B, q, :self.logprobs] = tl
+            if stp:  # last in the step: finished rows give the pad token, running rows count and match theirs
+                self._stop_st[b0], pred = stop_ref(self._stop_st[b0], pred, self.stop.stop_token_ids,
+                                                   self.stop.stop_sequences, self.stop.min_new_tokens,
+                                                   self.stop.pad_token_id)
             if out is not None and last_only:
                 out.copy_(pred)
                 pred = out

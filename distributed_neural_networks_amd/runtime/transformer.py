@@ -84,7 +84,7 @@ class TransformerStage(StageCompute):
                  fp8: bool = False, temperature: float = 0.0, top_k: int = 0, seed: int = 0,
                  kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
                  top_p: float = 1.0, min_p: float = 0.0, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0):
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0, stop=None):
         info = model_info(model)
         # fp8 weights, prefill (W8A8) activations: "e4m3" (default) = one e4m3
         # byte per activation, per-row scale, at the fp8 MFMA rate; "split" =
@@ -126,6 +126,16 @@ class TransformerStage(StageCompute):
         if not isinstance(logprobs, int) or isinstance(logprobs, bool) or not 0 <= logprobs <= T_.LOGPROBS_MAX_N:
             raise ValueError(f"logprobs must be an integer in [0, {T_.LOGPROBS_MAX_N}], got {logprobs!r}")
         self.logprobs = logprobs if last else 0
+        # stop conditions (last stage; config.StopConfig or None): per-row device state updated by a launch of
+        # its own behind the argmax / sampler, and with min_new_tokens a suppression launch in front of it
+        # (csrc/kernels/stop.hip); None = nothing allocated, nothing launched
+        self.stop = stop if last else None
+        if self.stop is not None:
+            V = info.cfg.vocab_size
+            bad = [i for i in self.stop.stop_token_ids + tuple(e for q in self.stop.stop_sequences for e in q)
+                   + (self.stop.pad_token_id,) if not 0 <= i < V]
+            if bad:
+                raise ValueError(f"stop: ids outside [0, {V}): {bad!r}")
         self.model, self.family, self.cfg = model, info.family, info.cfg
         self.start, self.end, self.first, self.last = start, end, first, last
         self.device = dev = torch.device(device)
@@ -407,6 +417,44 @@ class TransformerStage(StageCompute):
         if self.logprobs:
             self.lp_ws = T_.logprobs_workspace(self.max_batch, self.V, self.logprobs, dev)
 
+        # stop conditions: g, the finish record and the window of every KV row
+        self.stop_state = T_.stop_state(self.max_batch, dev) if self.stop is not None else None
+
+    # ------------------------------------------------------------------ stop conditions
+    def stop_begin(self, b0: int, B: int) -> None:
+        """Start a generation on cache rows [b0, b0 + B): nothing generated,
+        nothing finished, an empty window."""
+        if self.stop is None:
+            raise ValueError("stop_begin: this stage has no stop conditions")
+        if b0 < 0 or b0 + B > self.max_batch:
+            raise ValueError(f"stop_begin: rows [{b0}, {b0 + B}) outside the {self.max_batch} rows")
+        st = self.stop_state[b0:b0 + B]
+        st[:, :3].zero_()
+        st[:, 3:].fill_(-1)
+
+    def stop_forget(self, b0: int, B: int) -> None:
+        """After a prefill piece before the last one: its sample is discarded,
+        so it is neither counted nor matched (nothing has been generated yet:
+        the state goes back to the beginning)."""
+        self.stop_begin(b0, B)
+
+    def stop_snapshot(self, b0: int, B: int):
+        """A copy of the stop state of rows [b0, b0 + B) (graph capture runs the
+        decode body for real: ``DecodeRing.capture`` puts it back)."""
+        return b0, B, self.stop_state[b0:b0 + B].clone()
+
+    def stop_restore(self, snap) -> None:
+        b0, B, st = snap
+        self.stop_state[b0:b0 + B].copy_(st)
+
+    def _stop_rows(self, tokens, b0: int, rows: int, also, hist, adv) -> None:
+        """The stop launch, last in a ``last_only`` step: ``tokens`` (and
+        ``also`` / ``hist`` at the position before the tail's advance of
+        ``adv``) hold what the argmax / sampler launch just wrote."""
+        sp = self.stop
+        T_.stop_rows(tokens, self.stop_state[b0:b0 + rows], sp.stop_token_ids, sp.stop_sequences, sp.min_new_tokens,
+                     sp.pad_token_id, also=also, hist=hist, pos=adv if hist is not None else None, pos_off=-1)
+
     # ------------------------------------------------------------------ log-probabilities
     def bind_logprobs(self, b0: int, chosen: torch.Tensor, top_ids: torch.Tensor, top_lps: torch.Tensor) -> None:
         """The histories that steps on cache rows [b0, b0 + B) write (the caller
@@ -620,7 +668,11 @@ class TransformerStage(StageCompute):
         logits = self.logits[r0:r0 + rows]
         pen = self.penalties_on and last_only
         lpn = self.logprobs > 0 and last_only
-        if self.fuse_norm and last_only and not self.temperature > 0 and not pen:
+        stp = self.stop is not None and last_only
+        # min_new_tokens: the stop ids' logits are -inf while a row is below it, which the fused head + argmax
+        # (its argmax comes from the unsuppressed values) cannot honour
+        sup = stp and self.stop.min_new_tokens > 0 and len(self.stop.stop_token_ids) > 0
+        if self.fuse_norm and last_only and not self.temperature > 0 and not pen and not sup:
             # greedy: the head writes the logits and each workgroup's argmax
             # partials; one merge launch takes the ids and the step tail
             x_last = torch.as_strided(src, (rows, d), (ldx, 1))
@@ -630,6 +682,8 @@ class TransformerStage(StageCompute):
                            also, adv, hist):
                 if lpn:  # the head wrote the logits too
                     self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
+                if stp:
+                    self._stop_rows(dst, b0, rows, also, hist, adv)
                 return StageOutput(logits[:, :self.V], dst)
         if self.fuse_norm:
             x_last = torch.as_strided(src, (rows, d), (ldx, 1))
@@ -647,6 +701,9 @@ class TransformerStage(StageCompute):
             # penalised logits feed the unchanged argmax / sampler launches below (never the fused head, whose
             # argmax comes from the unpenalised values)
             self._penalise(logits, b0, rows, T)
+        if sup:
+            T_.stop_suppress(logits, self.V, self.stop_state[b0:b0 + rows], self.stop.stop_token_ids,
+                             self.stop.min_new_tokens)
         if self.temperature > 0 and last_only:
             if not T_.SAMPLE_FUSED_TAIL:  # the A/B baseline: sampler launch, then the ids copy (and the ring's tail launches)
                 if self.top_p < 1.0 or self.min_p > 0.0:
@@ -660,6 +717,8 @@ class TransformerStage(StageCompute):
                     self.pen_prev[b0:b0 + rows].copy_(nxt)
                 if lpn:
                     self._record_logprobs(logits, nxt, b0, rows, T, pos, False)
+                if stp:
+                    self._stop_rows(nxt, b0, rows, out, None, None)
                 return StageOutput(logits[:, :self.V], nxt)
             dst = out if out is not None else nxt
             also, adv, hist = _advance3(advance)
@@ -669,6 +728,8 @@ class TransformerStage(StageCompute):
                 self.pen_prev[b0:b0 + rows].copy_(dst)
             if lpn:
                 self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
+            if stp:
+                self._stop_rows(dst, b0, rows, also, hist, adv)
             return StageOutput(logits[:, :self.V], dst)
         dst = out if (last_only and out is not None) else nxt
         also, adv, hist = _advance3(advance)
@@ -680,6 +741,8 @@ class TransformerStage(StageCompute):
             self.pen_prev[b0:b0 + rows].copy_(dst)
         if lpn:
             self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
+        if stp:
+            self._stop_rows(dst, b0, rows, also, hist, adv)
         return StageOutput(logits[:, :self.V], dst)
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None):
@@ -729,7 +792,7 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                        temperature: float = 0.0, top_k: int = 0, seed: int = 0, kv_dtype: str = "bf16",
                        kv_scale: str = "calibrated", fp8_prefill: str = "e4m3", top_p: float = 1.0,
                        min_p: float = 0.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                       frequency_penalty: float = 0.0, logprobs: int = 0):
+                       frequency_penalty: float = 0.0, logprobs: int = 0, stop=None):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
     info = model_info(model)
     max_seq = min(max_seq, getattr(info.cfg, "block_size", getattr(info.cfg, "max_seq", max_seq)))
@@ -737,7 +800,7 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                             temperature, top_k, seed, kv_dtype=kv_dtype, kv_scale=kv_scale, fp8_prefill=fp8_prefill,
                             top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                            logprobs=logprobs)
+                            logprobs=logprobs, stop=stop)
 
 
 # ---------------------------------------------------------------------- smoke / golden check

@@ -281,6 +281,10 @@ PYBIND11_MODULE(_dnn_hip, m) {
     return dnn_stop_suppress(P(x), ld, M, N, CIP(state), stop_ids.data(), (int)stop_ids.size(), min_new, ST(st));
   }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("state"), py::arg("stop_ids"),
      py::arg("min_new"), py::arg("st"));
+  m.def("ragged_last_rows", [](u64 h, int ld, u64 lens, int t0, int Tc, int B, int d, u64 dst, int dst_ld, u64 st) {
+    return dnn_ragged_last_rows(CP(h), ld, CIP(lens), t0, Tc, B, d, P(dst), dst_ld, ST(st));
+  }, py::arg("h"), py::arg("ld"), py::arg("lens"), py::arg("t0"), py::arg("Tc"), py::arg("B"), py::arg("d"),
+     py::arg("dst"), py::arg("dst_ld"), py::arg("st"));
   m.def("quant_fp8_rows", [](u64 x, int ldx, u64 q, u64 scale, int M, int K, int kpad, u64 st, int split) {
     return dnn_quant_fp8_rows(CP(x), ldx, P(q), FP(scale), M, K, kpad, ST(st), split);
   }, py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("scale"), py::arg("M"), py::arg("K"), py::arg("kpad"),

@@ -174,6 +174,15 @@ int dnn_stop_rows(int* tok, int* also, int* hist, int hist_ld, const int* pos, i
                   int pad, int M, hipStream_t st);
 int dnn_stop_suppress(void* x, int ld, int M, int N, const int* state, const int* stop_ids, int n_ids, int min_new,
                       hipStream_t st);
+// ragged prompts (ragged.hip): one piece of a right-padded prefill covers prompt positions [t0, t0 + Tc) of B
+// sequences, its bf16 hidden states h as rows (b * Tc + t) of ld entries.  For sequence b with q = lens[b] -
+// 1 - t0 in [0, Tc) (its own last prompt position lies in this piece) row h[(b * Tc + q) * ld : +d] is copied
+// to dst[b * dst_ld : +d]; every other dst row, and the entries of a copied row past d, keep what they hold
+// (lens[b] <= 0 never matches).  -1, nothing launched: null h / lens / dst, d not a positive multiple of 8,
+// Tc <= 0, t0 < 0, ld or dst_ld below d or not a multiple of 8, h or dst not 16-byte aligned; -2: B > 2^24.
+// B <= 0 returns 0.
+int dnn_ragged_last_rows(const void* h, int ld, const int* lens, int t0, int Tc, int B, int d, void* dst, int dst_ld,
+                         hipStream_t st);
 int dnn_quant_fp8_rows(const void* x, int ldx, void* q, float* scale, int M, int K, int kpad, hipStream_t st,
                        int split = 0);
 int dnn_gemm_fp8(const void* A, const float* sa, const void* W, const float* sw, void* C, int ldc, const float* bias,

@@ -28,7 +28,7 @@ static void expect_noop(int rc, const char* what) {
 }
 
 int main() {
-  char buf[64] = {0};
+  alignas(16) char buf[64] = {0};
   void* p = buf;
   float* f = reinterpret_cast<float*>(buf);
   int* ip = reinterpret_cast<int*>(buf);
@@ -81,6 +81,15 @@ int main() {
   expect_reject(dnn_sample_topk(p, 12, 2, 12, ip, 1.f, 0, 1u, nullptr, st), "sample ld%8");
   expect_reject(dnn_argmax_rows(p, 12, 2, 12, ip, 0, st), "argmax bf16 ld%8");
   expect_noop(dnn_argmax_rows(p, 16, 0, 16, ip, 0, st), "argmax M=0");
+  // ragged prompts
+  expect_reject(dnn_ragged_last_rows(p, 16, ip, 0, 4, 2, 12, p, 16, st), "ragged d%8");
+  expect_reject(dnn_ragged_last_rows(p, 8, ip, 0, 4, 2, 16, p, 16, st), "ragged ld < d");
+  expect_reject(dnn_ragged_last_rows(p, 16, ip, 0, 4, 2, 16, p, 20, st), "ragged dst_ld%8");
+  expect_reject(dnn_ragged_last_rows(p, 16, nullptr, 0, 4, 2, 16, p, 16, st), "ragged without lens");
+  expect_reject(dnn_ragged_last_rows(p, 16, ip, -1, 4, 2, 16, p, 16, st), "ragged t0 < 0");
+  expect_reject(dnn_ragged_last_rows(p, 16, ip, 0, 0, 2, 16, p, 16, st), "ragged Tc=0");
+  expect_reject(dnn_ragged_last_rows(buf + 2, 16, ip, 0, 4, 2, 16, buf + 2, 16, st), "ragged misaligned rows");
+  expect_noop(dnn_ragged_last_rows(nullptr, 16, ip, 0, 4, 0, 16, p, 16, st), "ragged B=0");
   // CIFAR
   expect_reject(dnn_cifar_set_v4_pt(3), "v4 pt%4");
   expect_reject(dnn_cifar_set_v4_pt(36), "v4 pt>32");

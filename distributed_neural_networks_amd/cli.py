@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import checkpoint as ckpt
-from .config import ConfigError, NodeContext, banner, load_node
+from .config import DIST_TRANSPORTS, ConfigError, NodeContext, banner, load_node
 from .models import cifar, default_ranges, model_info
 from .utils.log import log, set_quiet
 
@@ -50,7 +50,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--input_image", help="Path to input image (only used by node with part_index 0)")
     # additive
     p.add_argument("--num_requests", type=int, default=1, help="requests stage 0 sends (default 1)")
-    p.add_argument("--prompt", default=None, help="GPT/Llama: comma-separated token ids (default: random)")
+    p.add_argument("--prompt", default=None, help="GPT/Llama: comma-separated token ids; ';' separates several prompts, cycled over the "
+                        "sequences (default: the config's 'prompts', else random)")
     p.add_argument("--shutdown_pipeline", action="store_true",
                    help="stage 0 asks all peers to exit after its requests complete")
     p.add_argument("--serve_seconds", type=float, default=None, help="non-initiating nodes exit after this long")
@@ -104,8 +105,14 @@ def load_image_u8(path: Optional[str], nid: str) -> torch.Tensor:
 
 
 def make_prompt(ctx: NodeContext, prompt: Optional[str]) -> torch.Tensor:
-    from .runtime.generate import make_prompts
-    return make_prompts(ctx.pipeline, prompt)
+    """The prompt batch of the gRPC request path: one full-prefix forward that
+    reads every row's prediction at the last position, so all prompts must
+    have one length (``check_prompt_transport``)."""
+    from .runtime.generate import make_prompt_batch
+    ids, lens = make_prompt_batch(ctx.pipeline, prompt)
+    if lens is not None:
+        raise ConfigError(RAGGED_NEEDS_RING.format(transport=ctx.pipeline.transport, lens=lens.tolist()))
+    return ids
 
 
 def kv_needs(ctx: NodeContext, args) -> Tuple[int, int]:
@@ -113,8 +120,10 @@ def kv_needs(ctx: NodeContext, args) -> Tuple[int, int]:
     config (``micro_batch_size`` x ``num_microbatches``; prompt + decode steps)."""
     pipe = ctx.pipeline
     T = pipe.prompt_len or pipe.seq_len
-    if getattr(args, "prompt", None):
-        T = len([v for v in args.prompt.split(",") if v.strip()])
+    from .runtime.generate import prompt_lists
+    given = prompt_lists(pipe, getattr(args, "prompt", None))  # --prompt, else the config's prompts
+    if given is not None:
+        T = max(len(q) for q in given)  # the longest prompt
     return pipe.micro_batch_size * pipe.num_microbatches, T + max(1, pipe.decode_steps or 1)
 
 
@@ -128,6 +137,30 @@ def check_config_capacity(ctx: NodeContext, args) -> None:
     limit = getattr(info.cfg, "block_size", None) or getattr(info.cfg, "max_seq", None)
     if limit is not None and n_pos > limit:
         raise ConfigError(f"ERROR: prompt + decode_steps = {n_pos} positions exceeds the model's limit {limit}")
+
+
+RAGGED_TRANSPORTS = ("colocated",) + DIST_TRANSPORTS  # the transports that generate through the decode ring
+RAGGED_NEEDS_RING = ("ERROR: prompts of different lengths {lens} need transport 'colocated', 'rccl', 'gloo' or "
+                     "'gloo_gpu' (the decode ring), got '{transport}': its request path reads every row's prediction at "
+                     "the last position of the padded batch")
+
+
+def check_prompt_transport(ctx: NodeContext, args) -> None:
+    """Reject, before any weight is loaded, prompts of different lengths
+    (``--prompt "a,b;c"`` or the config's ``prompts``) on a transport that
+    does not generate through the decode ring: the gRPC request path runs one
+    full-prefix forward and takes every row's prediction from position T - 1,
+    which for a shorter row is a pad position."""
+    pipe = ctx.pipeline
+    if model_info(pipe.model).family == "cifar" or pipe.transport in RAGGED_TRANSPORTS:
+        return
+    from .runtime.generate import prompt_lists
+    given = prompt_lists(pipe, getattr(args, "prompt", None))
+    if given is None:
+        return
+    lens = [len(given[i % len(given)]) for i in range(pipe.micro_batch_size * pipe.num_microbatches)]
+    if len(set(lens)) > 1:
+        raise ConfigError(RAGGED_NEEDS_RING.format(transport=pipe.transport, lens=lens))
 
 
 # --------------------------------------------------------------------------- stages
@@ -630,6 +663,7 @@ def main(argv=None) -> int:
         ctx = load_node(args.config, nid, _replica_arg(args))
         log(f"Loaded configuration from {args.config}")
         check_config_capacity(ctx, args)
+        check_prompt_transport(ctx, args)
         device = pick_device(ctx, args.device)
     except ConfigError as e:
         print(str(e), flush=True)

@@ -11,7 +11,7 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
   stages (GPT-2 4-stage, Llama-3 8-stage) can be described with this schema.
 * Additive optional fields (absent in the reference file, so it still loads):
   top level ``model``, ``dtype``, ``transport``, ``micro_batch_size``,
-  ``num_microbatches``, ``seq_len``, ``decode_steps``, ``prompt_len``, ``temperature``, ``top_k``,
+  ``num_microbatches``, ``seq_len``, ``decode_steps``, ``prompt_len``, ``prompts``, ``temperature``, ``top_k``,
   ``top_p``, ``min_p``, ``seed``, ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``,
   ``logprobs``, ``eos_token_id``, ``stop_token_ids``, ``stop_sequences``, ``min_new_tokens``,
   ``pad_token_id``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
@@ -130,6 +130,25 @@ def make_stop(vocab: int, eos_token_id: Any = None, stop_token_ids: Any = None, 
     return StopConfig(tuple(ids), tuple(seqs), int(min_new_tokens), pad)
 
 
+def make_prompt_lists(vocab: int, prompts: Any, n_seq: int, key: str = "prompts") -> Tuple[Tuple[int, ...], ...]:
+    """Validate the prompts of one generation (config key ``prompts``, or the
+    parsed ``--prompt``): a list of 1..``n_seq`` non-empty lists of ids in
+    ``[0, vocab)``.  Sequence i of the run gets entry ``i % n``, so one prompt
+    replicates to every sequence."""
+    if (not isinstance(prompts, (list, tuple)) or not prompts
+            or any(not isinstance(q, (list, tuple)) or any(not _is_int(e) for e in q) for q in prompts)):
+        raise ConfigError(f"ERROR: '{key}' must be a non-empty list of lists of integers, got {prompts!r}")
+    if len(prompts) > n_seq:
+        raise ConfigError(f"ERROR: '{key}' holds {len(prompts)} prompts, the run has micro_batch_size * "
+                          f"num_microbatches = {n_seq} sequences")
+    if any(len(q) == 0 for q in prompts):
+        raise ConfigError(f"ERROR: '{key}' holds an empty prompt: every prompt needs at least one id")
+    bad = [e for q in prompts for e in q if not 0 <= e < vocab]
+    if bad:
+        raise ConfigError(f"ERROR: '{key}' holds ids outside [0, {vocab}): {bad[:8]!r}")
+    return tuple(tuple(int(e) for e in q) for q in prompts)
+
+
 STOP_KEYS = ("eos_token_id", "stop_token_ids", "stop_sequences", "min_new_tokens", "pad_token_id")
 
 
@@ -151,6 +170,7 @@ class PipelineConfig:
     num_microbatches: int = 1
     seq_len: int = 64
     prompt_len: Optional[int] = None
+    prompts: Optional[Tuple[Tuple[int, ...], ...]] = None  # token ids of 1..n prompts, cycled over the sequences
     decode_steps: int = 0
     prefill_chunk: int = 0                    # > 0: chunked prefill, this many prompt tokens per stage call
     temperature: float = 0.0                  # 0 = greedy; > 0 = sampling (last stage)
@@ -336,6 +356,13 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
                                 ("frequency_penalty", pens["frequency_penalty"], 0)):
             if v != neutral:
                 raise ConfigError(f"ERROR: '{key}' {v!r} exists for the generating models only, got model '{model}'")
+    prompts = None
+    if cfg.get("prompts") is not None:
+        if model == "cifar10":
+            raise ConfigError(f"ERROR: 'prompts' exists for the generating models only, got model '{model}'")
+        from .models import model_info  # the vocabulary (imports torch: only when the key is present)
+        prompts = make_prompt_lists(model_info(model).cfg.vocab_size, cfg.get("prompts"),
+                                    int(cfg.get("micro_batch_size", 1)) * int(cfg.get("num_microbatches", 1)))
     idt = cfg.get("input_dtype", "fp32")
     if idt not in ("fp32", "uint8"):
         raise ConfigError(f"ERROR: 'input_dtype' must be 'fp32' or 'uint8', got {idt!r}")
@@ -361,7 +388,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         kv_cache_scale=kvs, fp8_prefill=fpp,
         transport=transport, micro_batch_size=int(cfg.get("micro_batch_size", 1)),
         num_microbatches=int(cfg.get("num_microbatches", 1)), seq_len=int(cfg.get("seq_len", 64)),
-        prompt_len=cfg.get("prompt_len"), decode_steps=int(cfg.get("decode_steps", 0)),
+        prompt_len=cfg.get("prompt_len"), prompts=prompts, decode_steps=int(cfg.get("decode_steps", 0)),
         prefill_chunk=int(cfg.get("prefill_chunk", 0)),
         temperature=float(cfg.get("temperature", 0.0)), top_k=int(cfg.get("top_k", 0)), seed=int(cfg.get("seed", 0)),
         top_p=float(tp), min_p=float(mp), repetition_penalty=float(rp), presence_penalty=pens["presence_penalty"],

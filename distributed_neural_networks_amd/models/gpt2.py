@@ -173,8 +173,14 @@ class GPTStage(nn.Module):
             self.ln_f = nn.LayerNorm(cfg.n_embd, bias=cfg.bias)
             self.lm_head = nn.Linear(cfg.n_embd, cfg.vocab_size, bias=False)
 
+    def head(self, x: torch.Tensor) -> torch.Tensor:
+        """Last stage: ``ln_f`` + ``lm_head`` on hidden states (..., n_embd)."""
+        return self.lm_head(self.ln_f(x))
+
     def forward(self, x: torch.Tensor, kv: Optional[List] = None, pos: int = 0,
-                last_only: bool = False) -> torch.Tensor:
+                last_only: bool = False, head: bool = True) -> torch.Tensor:
+        """``head=False`` (last stage): the hidden states behind the blocks,
+        without ``ln_f`` / ``lm_head`` (``head()`` applies them)."""
         if self.first:
             B, T = x.shape
             assert pos + T <= self.config.block_size, "Cannot forward, model block size is exhausted."
@@ -182,10 +188,10 @@ class GPTStage(nn.Module):
             x = self.wte(x) + self.wpe(p)
         for j, blk in enumerate(self.h):
             x = blk(x, None if kv is None else kv[j], pos)
-        if self.last:
+        if self.last and head:
             if last_only:
                 x = x[:, -1:, :]
-            x = self.lm_head(self.ln_f(x))
+            x = self.head(x)
         return x
 
 

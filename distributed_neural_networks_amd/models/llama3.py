@@ -152,16 +152,22 @@ class LlamaStage(nn.Module):
             self._rope = rope_tables(self.config, max(seq, 16), device)
         return self._rope
 
-    def forward(self, x, kv: Optional[List] = None, pos: int = 0, last_only: bool = False):
+    def head(self, x):
+        """Last stage: ``norm`` + ``lm_head`` on hidden states (..., n_embd)."""
+        return self.lm_head(self.norm(x))
+
+    def forward(self, x, kv: Optional[List] = None, pos: int = 0, last_only: bool = False, head: bool = True):
+        """``head=False`` (last stage): the hidden states behind the layers,
+        without ``norm`` / ``lm_head`` (``head()`` applies them)."""
         if self.first:
             x = self.embed_tokens(x)
         cos, sin = self.rope(pos + x.shape[1], x.device)
         for j, layer in enumerate(self.layers):
             x = layer(x, cos, sin, None if kv is None else kv[j], pos)
-        if self.last:
+        if self.last and head:
             if last_only:
                 x = x[:, -1:, :]
-            x = self.lm_head(self.norm(x))
+            x = self.head(x)
         return x
 
 

@@ -511,3 +511,39 @@ def stop_suppress(logits: torch.Tensor, n_vocab: int, state: torch.Tensor, stop_
     check(lib().stop_suppress(x=ptr(logits), ld=ld, M=M, N=int(n_vocab), state=ptr(state), stop_ids=ids,
                               min_new=int(min_new), st=stream_ptr()), "stop_suppress")
     return logits
+
+
+def ragged_last_rows(h: torch.Tensor, lens: torch.Tensor, t0: int, Tc: int, B: int, dst: torch.Tensor,
+                     d: Optional[int] = None) -> torch.Tensor:
+    """Ragged prompts (ragged.hip; mirror ``runtime/sampling.ragged_last_rows_ref``):
+    ``h`` bf16 (>= B * Tc, >= d) holds one prefill piece's hidden states, prompt
+    positions ``[t0, t0 + Tc)`` of B sequences (row ``b * Tc + t``); ``lens``
+    int32 (>= B) the prompt lengths.  Row ``b`` of ``dst`` bf16 (>= B, >= d)
+    takes ``h[b * Tc + q, :d]`` when ``q = lens[b] - 1 - t0`` lies in
+    ``[0, Tc)``; every other row keeps what it holds.  ``d`` defaults to the
+    width of ``dst``."""
+    for t, nm in ((h, "h"), (dst, "dst")):
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1:
+            raise TypeError(f"ragged_last_rows: {nm} must be bf16 (rows, width) with contiguous rows, got {t.dtype} "
+                            f"{tuple(t.shape)}")
+    B, Tc, t0 = int(B), int(Tc), int(t0)
+    d = dst.shape[1] if d is None else int(d)
+    if B < 1 or Tc < 1 or t0 < 0:
+        raise ValueError(f"ragged_last_rows: B = {B}, Tc = {Tc} must be >= 1 and t0 = {t0} >= 0")
+    if d < 8 or d % 8 or d > h.shape[1] or d > dst.shape[1]:
+        raise ValueError(f"ragged_last_rows: d = {d} must be a multiple of 8 within the widths {h.shape[1]} and "
+                         f"{dst.shape[1]}")
+    if h.shape[0] < B * Tc or dst.shape[0] < B:
+        raise ValueError(f"ragged_last_rows: h holds {h.shape[0]} rows (B * Tc = {B * Tc} needed), dst {dst.shape[0]} "
+                         f"(B = {B} needed)")
+    if lens.dtype != torch.int32 or lens.numel() < B or not lens.is_contiguous():
+        raise ValueError(f"ragged_last_rows: lens must be contiguous int32 with >= {B} entries")
+    if h.device != dst.device or lens.device != h.device:
+        raise ValueError("ragged_last_rows: h, lens and dst must be on one device")
+    ld = h.stride(0) if h.shape[0] > 1 else h.shape[1]
+    dst_ld = dst.stride(0) if dst.shape[0] > 1 else dst.shape[1]
+    if ld % 8 or dst_ld % 8 or ld < d or dst_ld < d or h.data_ptr() % 16 or dst.data_ptr() % 16:
+        raise ValueError("ragged_last_rows: rows must start 16-byte aligned (row strides multiples of 8, >= d)")
+    check(lib().ragged_last_rows(h=ptr(h), ld=ld, lens=ptr(lens), t0=t0, Tc=Tc, B=B, d=d, dst=ptr(dst),
+                                 dst_ld=dst_ld, st=stream_ptr()), "ragged_last_rows")
+    return dst

@@ -25,7 +25,8 @@ All share one contract, stated here for RCCL:
 Every link counts messages and bytes (``stats``) for the METRICS line.
 Message framing for open-ended streams (the CLI): a 4 x int64 header
 ``[kind, a, b, tag]`` precedes a request (``KIND_DATA``) or ends the stream
-(``KIND_STOP``).  Static schedules (benchmarks, microbatches of one request)
+(``KIND_STOP``); a generation whose prompts come with per-sequence lengths
+announces itself with ``KIND_RAGGED`` (``runtime/generate.py``).  Static schedules (benchmarks, microbatches of one request)
 move payloads without headers.
 """
 from __future__ import annotations
@@ -36,7 +37,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-KIND_DATA, KIND_STOP = 1, 2
+KIND_DATA, KIND_STOP, KIND_RAGGED = 1, 2, 3
 
 
 class P2PLink:

@@ -307,6 +307,24 @@ def stop_suppress_ref(logits: torch.Tensor, state: torch.Tensor, stop_ids, min_n
     return x
 
 
+# ---------------------------------------------------------------------- ragged prompts
+def ragged_last_rows_ref(h: torch.Tensor, lens: torch.Tensor, t0: int, Tc: int, B: int, d: int,
+                         dst: torch.Tensor) -> torch.Tensor:
+    """Torch mirror of ``dnn_ragged_last_rows`` (csrc/kernels/ragged.hip): ``h``
+    (>= B * Tc, >= d) holds the hidden states of prompt positions
+    ``[t0, t0 + Tc)`` of B sequences, row ``b * Tc + t``.  A copy of ``dst``
+    (>= B, >= d) in which row ``b`` took ``h[b * Tc + q, :d]`` when
+    ``q = lens[b] - 1 - t0`` lies in ``[0, Tc)``: the sequence's own last
+    prompt position falls into this piece.  Every other row, and the columns
+    past ``d``, keep what they held; ``lens[b] <= 0`` never matches."""
+    out = dst.clone()
+    q = lens.detach().to(device=h.device, dtype=torch.int64).reshape(-1)[:B] - 1 - int(t0)
+    hit = (q >= 0) & (q < int(Tc))
+    rows = torch.arange(B, dtype=torch.int64, device=h.device)[hit]
+    out[rows, :d] = h[rows * int(Tc) + q[hit], :d].to(out.dtype)
+    return out
+
+
 def pick(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0,
          step: Optional[torch.Tensor] = None, top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
     """Greedy when temperature <= 0, else the Gumbel sample over the top-k /

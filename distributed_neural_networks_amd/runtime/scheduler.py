@@ -294,6 +294,15 @@ def _act_dtype(st) -> torch.dtype:
     return getattr(st, "act_dtype", torch.bfloat16)
 
 
+def _window(hist: torch.Tensor, base, n: int) -> torch.Tensor:
+    """Columns ``[base, base + n)`` of a per-position history (B, L[, k]);
+    ``base`` an int, or after ragged prompts a host (B,) tensor: row b's own."""
+    if not isinstance(base, torch.Tensor):
+        return hist[:, base:base + n]
+    idx = base.to(hist.device)[:, None] + torch.arange(n, device=hist.device)[None, :]
+    return hist[torch.arange(hist.shape[0], device=hist.device)[:, None], idx]
+
+
 class DecodeRing:
     """Microbatched autoregressive decode over a pipeline of stage groups.
 
@@ -306,7 +315,8 @@ class DecodeRing:
 
     def __init__(self, stages: Sequence, links: RingLinks, n_groups: int, M: int, B: int,
                  use_graphs: bool = True, record: bool = True, progress: Progress = None, lanes: int = 0,
-                 multi_step: int = -1, forward_prompt_ids: bool = False, early_exit: bool = True):
+                 multi_step: int = -1, forward_prompt_ids: bool = False, early_exit: bool = True,
+                 ragged: bool = False):
         """``early_exit`` (one group, a last stage with stop conditions):
         ``decode_rounds`` returns once every row of every microbatch has
         finished (checked every K rounds, one check behind: see there).
@@ -317,6 +327,13 @@ class DecodeRing:
         has, so before a microbatch's first prefill piece rank 0 sends its
         (B, T) int32 ids down the stage links, the middle ranks pass them on
         and the last rank marks them (``penalty_begin``).
+
+        ``ragged`` (more than one group; every rank passes the same value, like
+        ``forward_prompt_ids``): the prompts of this ring's generations come
+        with per-sequence lengths (``prefill(lens=...)``), so before a
+        microbatch's first prefill piece rank 0 sends its (B,) int32 lengths
+        down the stage links, in front of the prompt ids when those travel
+        too, and the middle ranks pass them on.
 
         ``lanes`` (one group, M > 1, GPU): the M microbatch steps of a round
         replay on this many HIP streams (0 = one stream, -1 = min(M, 4));
@@ -388,12 +405,14 @@ class DecodeRing:
         cap = min((getattr(s, "max_seq", 0) for s in self.stages), default=0)
         self.hist = ([torch.zeros((B, cap), dtype=torch.int32, device=dev) for _ in range(M)]
                      if n_groups == 1 and tail and cap > 0 and dev.type == "cuda" else None)
-        self.hist_base = [0] * M  # position of the first decode token of the current generation
+        # position of the first decode token of the current generation (ragged prompts: a host (B,) tensor)
+        self.hist_base = [0] * M
         self.hist_n = [0] * M  # decode tokens recorded in hist since then
         # last stage with repetition / presence / frequency penalties: its per-row state starts at the prompt
         # (_prefill) and survives the capture runs through snapshots (capture)
         self.pen = self.stages[-1] if self.last and getattr(self.stages[-1], "penalties_on", False) else None
         self.forward_prompt_ids = bool(forward_prompt_ids) and n_groups > 1
+        self.ragged = bool(ragged) and n_groups > 1
         if self.pen is not None and n_groups > 1 and not self.forward_prompt_ids:
             raise ValueError("a last stage with penalties on a ring of several groups needs forward_prompt_ids=True "
                              "on every rank (the prompt ids live on group 0)")
@@ -405,7 +424,8 @@ class DecodeRing:
         # real replay overwrites every one of them before ``logprobs()`` reads it, exactly as with ``hist``.
         self.lp_n = int(getattr(self.stages[-1], "logprobs", 0) or 0) if self.last else 0
         self.lp_chosen = self.lp_top_ids = self.lp_top_lps = None
-        self.lp_base = [0] * M  # position of the first recorded token of the current generation
+        # position of the first recorded token of the current generation (ragged prompts: a host (B,) tensor)
+        self.lp_base = [0] * M
         self.lp_cnt = [0] * M  # tokens recorded since then
         if self.lp_n:
             if self.lanes:
@@ -436,11 +456,14 @@ class DecodeRing:
         self._fin_i = 0  # checks queued in the current generation
 
     # -- one microbatch through this rank's stages --------------------------
-    def _run(self, x, m: int, T: int, out=None, advance=None):
+    def _run(self, x, m: int, T: int, out=None, advance=None, lens=None, t0: int = 0):
         h = x
         n = len(self.stages)
         for j, s in enumerate(self.stages):
-            if j == n - 1 and advance is not None:
+            if lens is not None:  # a piece of a ragged prefill: a last stage keeps hidden rows and samples nothing
+                h = s.step(h, self.pos[m], self.B, T, b0=m * self.B, out=out if j == n - 1 and not self.last else None,
+                           lens=lens, t0=t0)
+            elif j == n - 1 and advance is not None:
                 h = s.step(h, self.pos[m], self.B, T, b0=m * self.B, out=out, advance=advance)
             else:
                 h = s.step(h, self.pos[m], self.B, T, b0=m * self.B, out=out if j == n - 1 else None)
@@ -515,12 +538,24 @@ class DecodeRing:
         self.rorder.waited(m)
 
     # -- prefill ----------------------------------------------------------------
-    def prefill(self, prompts: Optional[Sequence[torch.Tensor]], T: int, chunk: int = 0) -> None:
+    def prefill(self, prompts: Optional[Sequence[torch.Tensor]], T: int, chunk: int = 0,
+                lens: Optional[Sequence[torch.Tensor]] = None) -> None:
         """Run the T-token prompts of all M microbatches (group 0 passes
         ``prompts[m]`` (B, T) int; other groups pass None).  ``chunk`` > 0
         prefills in pieces of that many tokens (chunked prefill: activation
         buffers and stage hops stay bounded for long prompts; each piece
         attends to the cache written by the previous ones).
+
+        ``lens`` (ragged prompts; group 0 passes ``lens[m]`` (B,) int, other
+        groups None and ``ragged=True`` at construction): sequence b of
+        microbatch m has a prompt of ``1 <= lens[m][b] <= T`` tokens, right-
+        padded to T.  Causal attention keeps the pads out of every valid
+        position; each row's first token comes from its own last prompt
+        position (``ragged_first_token``), the row then decodes from position
+        ``lens[m][b]``, and its decode steps overwrite the K / V the pads wrote
+        there before any step reads them.  Microbatch m runs only the pieces
+        that start below its own longest prompt, the last one cut to it.  The
+        ragged path runs whenever ``lens`` is given, equal lengths included.
 
         Stages with a calibrated fp8 KV cache that is not calibrated yet
         (``needs_kv_calibration``: the same on every rank, it follows the
@@ -529,15 +564,35 @@ class DecodeRing:
         their per-layer scales from the cache's K / V amax after each and
         clearing it; then the prefill runs for real.  Once per stage lifetime."""
         while any(getattr(s, "needs_kv_calibration", False) for s in self.stages):
-            self._prefill(prompts, T, chunk)
+            self._prefill(prompts, T, chunk, lens)
             self.drain()
             for s in self.stages:
                 if getattr(s, "needs_kv_calibration", False):
                     s.calibrate_kv()
-        self._prefill(prompts, T, chunk)
+        self._prefill(prompts, T, chunk, lens)
 
-    def _prefill(self, prompts, T: int, chunk: int = 0) -> None:
+    def _lens_of(self, lens, m: int, T: int) -> torch.Tensor:
+        """The checked (B,) int32 lengths of microbatch m on the device: what
+        group 0 was given (``lens[m]``), or on the other groups what arrived
+        over the stage link (``lens`` None).  Every rank checks them against
+        the same T, so a length that would give this rank other pieces than
+        its sender's raises here instead of stalling the links."""
+        if lens is not None:
+            ln = torch.as_tensor(lens[m]).reshape(-1).to(torch.int32)
+        else:
+            ln = torch.empty((self.B,), dtype=torch.int32, device=self.dev)
+            self.links.prev.recv(ln)
+        if ln.numel() != self.B or int(ln.min()) < 1 or int(ln.max()) > T:
+            raise ValueError(f"prefill: the lengths of microbatch {m} must be {self.B} values in [1, {T}], got "
+                             f"{ln.tolist()}")
+        return ln.to(self.dev).contiguous()
+
+    def _prefill(self, prompts, T: int, chunk: int = 0, lens=None) -> None:
         B, d = self.B, self.d
+        if self.first and self.G > 1 and (lens is not None) != self.ragged:
+            raise ValueError("prefill: per-sequence lengths on a ring of several groups need ragged=True on every rank "
+                             "(and a ring built with ragged=True expects them)")
+        rag = lens is not None if self.first else self.ragged
         C = T if chunk <= 0 else min(chunk, T)
         pieces = [(t0, min(C, T - t0)) for t0 in range(0, T, C)]
         for m in range(self.M):
@@ -557,6 +612,13 @@ class DecodeRing:
         n_sent = 0
         id_work: List[tuple] = []  # (work, tensor) of the prompt ids on their way down the stage links
         for m in range(self.M):
+            ln, Tm = None, T  # ln None: the equal-length path
+            if rag:
+                ln = self._lens_of(lens if self.first else None, m, T)
+                if not self.last:
+                    id_work.append((self.links.nxt.isend(ln), ln))
+                Tm = int(ln.max())  # every rank derives the same pieces from the lengths it received
+                pieces = [(t0, min(C, Tm - t0)) for t0 in range(0, Tm, C)]
             if self.first:
                 ids = prompts[m].to(device=self.dev, dtype=torch.int32).contiguous()
             elif self.forward_prompt_ids:
@@ -570,10 +632,10 @@ class DecodeRing:
             if self.pen is not None:
                 # the whole prompt is marked before its first token is sampled (chunked prefill and the
                 # fp8-KV calibration prefills included: each starts from the prompt alone)
-                self.pen.penalty_begin(m * B, ids)
+                self.pen.penalty_begin(m * B, ids, lens=ln)
             self._out_ready(m)
             for t0, Tc in pieces:
-                final = t0 + Tc == T
+                final = t0 + Tc == Tm
                 if self.first:
                     x = ids[:, t0:t0 + Tc].contiguous()
                 else:
@@ -583,24 +645,31 @@ class DecodeRing:
                 if not self.last and pf_work[k] is not None:
                     pf_work[k].wait()
                 with trace.span("prefill", "compute", mb=m, t0=t0):
-                    y = self._run(x, m, Tc, out=(self.out[m] if self.last else out_pf[k][:B * Tc]))
-                self.pos[m].add_(Tc)
-                if self.pen is not None and not final:
-                    self.pen.penalty_forget(m * B, B)  # this piece's sample is discarded, never counted
-                if self.stp is not None and not final:
-                    self.stp.stop_forget(m * B, B)  # ... and neither counted nor matched as a generated token
+                    y = self._run(x, m, Tc, out=(self.out[m] if self.last else out_pf[k][:B * Tc]), lens=ln, t0=t0)
+                if rag and final:
+                    self.pos[m].copy_(ln)  # each row decodes from its own length
+                    if self.last:  # nothing was sampled so far: every row's first token, in one tail
+                        self.stages[-1].ragged_first_token(m * B, B, ln, out=self.out[m])
+                else:
+                    self.pos[m].add_(Tc)
+                if not rag and not final:  # (a ragged piece samples nothing: nothing to forget)
+                    if self.pen is not None:
+                        self.pen.penalty_forget(m * B, B)  # this piece's sample is discarded, never counted
+                    if self.stp is not None:
+                        self.stp.stop_forget(m * B, B)  # ... and neither counted nor matched as a generated token
                 if not self.last:
                     pf_work[k] = self.links.nxt.isend(out_pf[k][:B * Tc])
                     n_sent += 1
                 elif final:
                     self.n_gen[m] = 1
                     if self.lp_chosen is not None:
-                        self.lp_base[m], self.lp_cnt[m] = T - 1, 1  # the prompt's last position gave the first token
+                        # the prompt's last position gave the first token
+                        self.lp_base[m], self.lp_cnt[m] = (ln.cpu().long() - 1 if rag else T - 1), 1
                     if self.G == 1:
                         self.cur[m].copy_(self.out[m].view(B, 1))
                         if self.record:
                             self.toks[m].append(self.out[m].clone())
-                            self.hist_base[m], self.hist_n[m] = T, 0
+                            self.hist_base[m], self.hist_n[m] = (ln.cpu().long() if rag else T), 0
                     else:
                         self._send(m)
                 self.progress()
@@ -814,14 +883,14 @@ class DecodeRing:
         self.sorder.drained()
         self.rorder.drained()  # decode_rounds never leaves a receive posted past its last item
 
-    def generate(self, prompts, T: int, steps: int, chunk: int = 0) -> Optional[torch.Tensor]:
+    def generate(self, prompts, T: int, steps: int, chunk: int = 0, lens=None) -> Optional[torch.Tensor]:
         """Prefill + ``steps - 1`` decode rounds (``steps`` tokens per sequence).
         Group 0 returns (M*B, steps) int32 on the host; other groups None.
         With stop conditions the columns past a row's length (``finished()``)
         hold ``pad_token_id``, and with ``early_exit`` the result is
         (M*B, steps_run), steps_run <= steps: the ring stopped once every row
-        had finished."""
-        self.prefill(prompts, T, chunk)
+        had finished.  ``lens``: per-sequence prompt lengths (``prefill``)."""
+        self.prefill(prompts, T, chunk, lens)
         if steps > 1:
             self.capture()
         if steps > 1:
@@ -841,8 +910,7 @@ class DecodeRing:
         for m, t in enumerate(self.toks):
             parts = [torch.stack(t, 1)] if t else []
             if self.hist is not None and self.hist_n[m]:
-                b = self.hist_base[m]
-                parts.append(self.hist[m][:, b:b + self.hist_n[m]])
+                parts.append(_window(self.hist[m], self.hist_base[m], self.hist_n[m]))
             rows.append(torch.cat(parts, 1))
         return torch.cat(rows, 0).cpu()
 
@@ -883,7 +951,7 @@ class DecodeRing:
         out = {"chosen": [], "top_ids": [], "top_lps": []}
         for m in range(self.M):
             b, c = self.lp_base[m], self.lp_cnt[m]
-            out["chosen"].append(self.lp_chosen[m][:, b:b + c])
-            out["top_ids"].append(self.lp_top_ids[m][:, b:b + c])
-            out["top_lps"].append(self.lp_top_lps[m][:, b:b + c])
+            out["chosen"].append(_window(self.lp_chosen[m], b, c))
+            out["top_ids"].append(_window(self.lp_top_ids[m], b, c))
+            out["top_lps"].append(_window(self.lp_top_lps[m], b, c))
         return {k: torch.cat(v, 0).cpu() for k, v in out.items()}

@@ -248,13 +248,19 @@ class TorchStage(StageCompute):
     def act_dtype(self) -> torch.dtype:
         return self.dtype
 
-    def penalty_begin(self, b0: int, ids: torch.Tensor) -> None:
+    def penalty_begin(self, b0: int, ids: torch.Tensor, lens=None) -> None:
         """Start a generation on cache rows [b0, b0 + B): the (B, T) prompt's
-        tokens are marked, nothing is counted yet (``TransformerStage.penalty_begin``)."""
+        tokens are marked, nothing is counted yet (``TransformerStage.penalty_begin``).
+        ``lens`` (ragged prompts): only ``ids[b, :lens[b]]`` are marked."""
         from .sampling import penalty_state
         if not self.penalties_on:
             raise ValueError("penalty_begin: this stage has no penalties")
-        self._pen[b0] = penalty_state(ids, model_info(self.model).cfg.vocab_size)
+        V = model_info(self.model).cfg.vocab_size
+        if lens is None:
+            self._pen[b0] = penalty_state(ids, V)
+        else:
+            ls = [int(v) for v in torch.as_tensor(lens).reshape(-1).tolist()]
+            self._pen[b0] = torch.cat([penalty_state(ids[b:b + 1, :ls[b]], V) for b in range(ids.shape[0])], 0)
         self._pen_prev[b0] = None
 
     def penalty_forget(self, b0: int, B: int) -> None:
@@ -298,14 +304,31 @@ class TorchStage(StageCompute):
             raise ValueError("bind_logprobs: this stage records no log-probabilities")
         self._lp_hist[b0] = (chosen, top_ids, top_lps)
 
+    def _hidden(self, h, kv, p: int):
+        """The module's blocks (and embedding) without its head: (B, T, d)."""
+        return self.module(h, kv, p, head=False)
+
+    def _head(self, x):
+        return self.module.head(x)
+
     @torch.no_grad()
-    def step(self, x, pos, B: int, T: int, b0: int = 0, out=None, last_only: bool = True):
+    def step(self, x, pos, B: int, T: int, b0: int = 0, out=None, last_only: bool = True, lens=None, t0: int = 0):
         """KV-cached transformer step (CPU golden path; same contract as
         ``TransformerStage.step``): x = ids (B,T) on the first stage, else
-        hidden (B*T, d); ``pos`` = tokens already cached (uniform per batch);
-        rows ``[b0, b0+B)`` of the cache (one KV cache per microbatch offset)."""
+        hidden (B*T, d); ``pos`` = tokens already cached; rows ``[b0, b0+B)``
+        of the cache (one KV cache per microbatch offset).  Positions that
+        differ between the rows (decode after ragged prompts) run the rows one
+        at a time on row views of the cache.  ``lens`` (int (B,)): a piece of a
+        ragged prefill covering prompt positions ``[t0, t0 + T)``; the last
+        stage then samples nothing and keeps each row's hidden state of its
+        own last prompt position for ``ragged_first_token``."""
         cfg = model_info(self.model).cfg
-        p = int(pos[0]) if isinstance(pos, torch.Tensor) else int(pos)
+        if isinstance(pos, torch.Tensor):
+            ps = [int(v) for v in pos.reshape(-1)[:B].tolist()]
+        else:
+            ps = [int(pos)] * B
+        p = ps[0]
+        uniform = all(v == p for v in ps)
         caches = getattr(self, "_kv", None)
         if caches is None:
             caches = self._kv = {}
@@ -321,58 +344,100 @@ class TorchStage(StageCompute):
             h = x.to(torch.int64).view(B, T)
         else:
             h = x.view(B, T, cfg.n_embd).to(self.dtype)
-        y = self.module(h, kv, p, last_only=last_only)
+        if lens is not None and self.last:
+            from .sampling import ragged_last_rows_ref
+            hid = self._hidden(h, kv, p).reshape(B * T, cfg.n_embd)
+            keep = getattr(self, "_h_last", None)
+            if keep is None:
+                keep = self._h_last = {}
+            if b0 not in keep or keep[b0].shape[0] != B:
+                keep[b0] = torch.zeros((B, cfg.n_embd), dtype=self.dtype)
+            keep[b0] = ragged_last_rows_ref(hid, torch.as_tensor(lens), t0, T, B, cfg.n_embd, keep[b0])
+            return None
+        if uniform and not self.last:
+            y = self.module(h, kv, p)
+        elif uniform:
+            hid = self._hidden(h, kv, p)
+            y = self._head(hid[:, -1:, :] if last_only else hid)
+        else:
+            hid = torch.cat([self._hidden(h[b:b + 1], [(k[b:b + 1], v[b:b + 1]) for k, v in kv], ps[b])
+                             for b in range(B)], 0)
+            y = hid if not self.last else self._head(hid[:, -1:, :] if last_only else hid)
         if self.last:
-            from .sampling import pick
-            logits = y[:, -1, :] if last_only else y.reshape(B * T, -1)
             step = pos if isinstance(pos, torch.Tensor) else torch.full((B,), p, dtype=torch.int32)
-            if self.penalties_on and last_only:
-                # as the device stage: a decode step counts the rows' previous token, then every sampled
-                # position's logits (rounded to bf16) take the penalties
-                from .sampling import apply_penalties_ref, penalty_count
-                if b0 not in self._pen:
-                    raise ValueError(f"penalties: no penalty_begin for cache rows at {b0}")
-                if T == 1 and self._pen_prev[b0] is not None:
-                    self._pen[b0] = penalty_count(self._pen[b0], self._pen_prev[b0])
-                logits = apply_penalties_ref(logits, self._pen[b0], self.rep_pen, self.freq_pen, self.pres_pen)
-                y = logits[:, None, :]
-            stp = self.stop is not None and last_only
-            if stp:
-                from .sampling import stop_ref, stop_suppress_ref
-                if b0 not in self._stop_st or self._stop_st[b0].shape[0] != B:
-                    raise ValueError(f"stop: no stop_begin for the {B} cache rows at {b0}")
-                if self.stop.min_new_tokens > 0 and self.stop.stop_token_ids:
-                    logits = stop_suppress_ref(logits, self._stop_st[b0], self.stop.stop_token_ids,
-                                               self.stop.min_new_tokens)
-                    y = logits[:, None, :]
-            pred = pick(y[:, -1, :], self.temperature, self.top_k, self.seed, step, top_p=self.top_p,
-                        min_p=self.min_p).to(torch.int32)
-            if self.penalties_on and last_only:
-                self._pen_prev[b0] = pred.clone()
-            if self.logprobs and last_only:
-                from .sampling import logprobs_ref
-                if b0 not in self._lp_hist:
-                    raise ValueError(f"logprobs: no bind_logprobs for cache rows at {b0}")
-                chosen, top_ids, top_lps = self._lp_hist[b0]
-                q = p + T - 1
-                if 0 <= q < chosen.shape[1]:
-                    c, ti, tl = logprobs_ref(logits, pred, self.logprobs)
-                    chosen[:B, q] = c
-                    top_ids[:B, q, :self.logprobs] = ti
-                    top_lps[:B, q, :self.logprobs] = tl
-            if stp:  # last in the step: finished rows give the pad token, running rows count and match theirs
-                self._stop_st[b0], pred = stop_ref(self._stop_st[b0], pred, self.stop.stop_token_ids,
-                                                   self.stop.stop_sequences, self.stop.min_new_tokens,
-                                                   self.stop.pad_token_id)
-            if out is not None and last_only:
-                out.copy_(pred)
-                pred = out
-            return StageOutput(logits, pred)
+            return self._tail(y, b0, B, T, step, [v + T - 1 for v in ps], out, last_only)
         y = y.reshape(B * T, cfg.n_embd)
         if out is not None:
             out.view(B * T, cfg.n_embd).copy_(y)
             return out
         return y
+
+    @torch.no_grad()
+    def ragged_first_token(self, b0: int, B: int, lens, out=None) -> StageOutput:
+        """Last stage, after the last piece of a ragged prefill of cache rows
+        [b0, b0 + B): the tail of a ``last_only`` step on the hidden states the
+        pieces kept (each row's own last prompt position), so every row's first
+        token.  The sampler's step operand is 0 for every row, what an
+        unchunked equal-length prefill passes; the log-probabilities go to
+        history position ``lens - 1``."""
+        if not self.last:
+            raise ValueError("ragged_first_token: last stage only")
+        keep = getattr(self, "_h_last", {}).get(b0)
+        if keep is None or keep.shape[0] != B:
+            raise ValueError(f"ragged_first_token: no ragged prefill piece ran on the {B} cache rows at {b0}")
+        y = self._head(keep[:, None, :])
+        ls = [int(v) for v in torch.as_tensor(lens).reshape(-1)[:B].tolist()]
+        return self._tail(y, b0, B, 0, torch.zeros((B,), dtype=torch.int32), [v - 1 for v in ls], out, True)
+
+    def _tail(self, y, b0: int, B: int, T: int, step, lp_q, out, last_only: bool):
+        """What the last stage does with its head's output ``y`` (B, 1 or T, V):
+        penalties, suppression, pick, log-probabilities (row b at history
+        position ``lp_q[b]``), stop conditions.  ``T == 1`` marks a decode step
+        (it counts the rows' previous token)."""
+        from .sampling import pick
+        logits = y[:, -1, :] if last_only else y.reshape(y.shape[0] * y.shape[1], -1)
+        if self.penalties_on and last_only:
+            # as the device stage: a decode step counts the rows' previous token, then every sampled
+            # position's logits (rounded to bf16) take the penalties
+            from .sampling import apply_penalties_ref, penalty_count
+            if b0 not in self._pen:
+                raise ValueError(f"penalties: no penalty_begin for cache rows at {b0}")
+            if T == 1 and self._pen_prev[b0] is not None:
+                self._pen[b0] = penalty_count(self._pen[b0], self._pen_prev[b0])
+            logits = apply_penalties_ref(logits, self._pen[b0], self.rep_pen, self.freq_pen, self.pres_pen)
+            y = logits[:, None, :]
+        stp = self.stop is not None and last_only
+        if stp:
+            from .sampling import stop_ref, stop_suppress_ref
+            if b0 not in self._stop_st or self._stop_st[b0].shape[0] != B:
+                raise ValueError(f"stop: no stop_begin for the {B} cache rows at {b0}")
+            if self.stop.min_new_tokens > 0 and self.stop.stop_token_ids:
+                logits = stop_suppress_ref(logits, self._stop_st[b0], self.stop.stop_token_ids,
+                                           self.stop.min_new_tokens)
+                y = logits[:, None, :]
+        pred = pick(y[:, -1, :], self.temperature, self.top_k, self.seed, step, top_p=self.top_p,
+                    min_p=self.min_p).to(torch.int32)
+        if self.penalties_on and last_only:
+            self._pen_prev[b0] = pred.clone()
+        if self.logprobs and last_only:
+            from .sampling import logprobs_ref
+            if b0 not in self._lp_hist:
+                raise ValueError(f"logprobs: no bind_logprobs for cache rows at {b0}")
+            chosen, top_ids, top_lps = self._lp_hist[b0]
+            c, ti, tl = logprobs_ref(logits, pred, self.logprobs)
+            for b, q in enumerate(lp_q):
+                if 0 <= q < chosen.shape[1]:
+                    chosen[b, q] = c[b]
+                    top_ids[b, q, :self.logprobs] = ti[b]
+                    top_lps[b, q, :self.logprobs] = tl[b]
+        if stp:  # last in the step: finished rows give the pad token, running rows count and match theirs
+            self._stop_st[b0], pred = stop_ref(self._stop_st[b0], pred, self.stop.stop_token_ids,
+                                               self.stop.stop_sequences, self.stop.min_new_tokens,
+                                               self.stop.pad_token_id)
+        if out is not None and last_only:
+            out.copy_(pred)
+            pred = out
+        return StageOutput(logits, pred)
 
     @torch.no_grad()
     def forward(self, x, out=None):

@@ -399,6 +399,9 @@ class TransformerStage(StageCompute):
                 self.q8b = torch.empty((ntok * kpad_of(ffn),), dtype=torch.uint8, device=dev)
                 self.sx8b = torch.empty((mx_scale_bytes(ntok, kpad_of(ffn)),), dtype=torch.uint8, device=dev)
         if self.last:
+            # ragged prompts: each row's hidden state at its own last prompt position, and the sampler's
+            # step operand of their first token; allocated by the first step(lens=...) (_ragged_buffers)
+            self.h_last = self.zero_pos = None
             self.buf_lnf = torch.empty((ntok, d), dtype=bf, device=dev)
             self.logits = torch.empty((ntok, self.Vpad), dtype=bf, device=dev)
             self.next_ids = torch.empty((ntok,), dtype=torch.int32, device=dev)
@@ -489,9 +492,10 @@ class TransformerStage(StageCompute):
                          pos_off=T - 1 - (1 if advanced else 0))
 
     # ------------------------------------------------------------------ penalties
-    def penalty_begin(self, b0: int, ids: torch.Tensor) -> None:
+    def penalty_begin(self, b0: int, ids: torch.Tensor, lens: Optional[torch.Tensor] = None) -> None:
         """Start a generation on cache rows [b0, b0 + B): clear their state and
-        mark the tokens of the (B, T) prompt ``ids``.  Before the prompt's first
+        mark the tokens of the (B, T) prompt ``ids``; with ``lens`` (int (B,),
+        ragged prompts) only ``ids[b, :lens[b]]``.  Before the prompt's first
         prefill piece (prefill is not the hot path: torch zero_ + scatter_)."""
         if not self.penalties_on:
             raise ValueError("penalty_begin: this stage has no penalties")
@@ -502,6 +506,11 @@ class TransformerStage(StageCompute):
         st.zero_()
         # clamped like the embedding's lookup: a bad id cannot index outside the row
         idx = ids.to(device=self.device, dtype=torch.int64).clamp(0, self.V - 1)
+        if lens is not None:
+            # ragged prompts: a pad position marks the row's first token again (L_b >= 1), never the pad id
+            valid = (torch.arange(ids.shape[1], device=self.device)[None, :]
+                     < lens.to(device=self.device, dtype=torch.int64).reshape(B, 1))
+            idx = torch.where(valid, idx, idx[:, :1])
         st.scatter_(1, idx, -0x8000)
         self.pen_prev[b0:b0 + B].fill_(-1)
 
@@ -568,13 +577,22 @@ class TransformerStage(StageCompute):
         return self.last and (not self.temperature > 0 or T_.SAMPLE_FUSED_TAIL)
 
     def step(self, x: torch.Tensor, pos: torch.Tensor, B: int, T: int, b0: int = 0, out: Optional[torch.Tensor] = None,
-             last_only: bool = True, advance=None):
+             last_only: bool = True, advance=None, lens: Optional[torch.Tensor] = None, t0: int = 0):
         """Run this stage for B sequences x T new tokens at cache rows
         [b0, b0+B) and positions ``pos`` (device int32 (B,), tokens already
         cached).  Returns hidden (B*T, d) bf16, or StageOutput for the last stage.
         ``advance`` = (ids or None, positions[, token history]): last stage only
         (``fuses_step_tail``): the sampled ids are also written to ``ids`` and
-        ``positions += 1``, in the argmax / sampler launch."""
+        ``positions += 1``, in the argmax / sampler launch.
+        ``lens`` (device int32 (B,), ragged prompts): the call is a piece of a
+        right-padded prefill covering prompt positions [t0, t0 + T).  First and
+        middle stages run it as the padded step it is; the last stage runs its
+        blocks, gathers each row's hidden state of its own last prompt position
+        into ``h_last`` (csrc/kernels/ragged.hip) and samples nothing: no head,
+        no penalty, log-probability or stop launch (``ragged_first_token``
+        does that once, after the last piece).  Returns None there."""
+        if lens is not None and self.last and (advance is not None or not last_only):
+            raise ValueError("step(lens=...) is a prefill piece: no advance, last_only")
         if advance is not None and not (self.fuses_step_tail and last_only):
             raise ValueError("step(advance=...) needs a last stage that fuses the step tail, with last_only")
         ntok = B * T
@@ -661,10 +679,55 @@ class TransformerStage(StageCompute):
                 out.view(ntok, d).copy_(h)
                 return out
             return h
+        if lens is not None:
+            # a piece of a ragged prefill: nothing is sampled here; each row whose own last prompt position
+            # lies in [t0, t0 + T) leaves its hidden state for ragged_first_token
+            self._ragged_buffers()
+            T_.ragged_last_rows(h, lens, t0, T, B, self.h_last[b0:b0 + B])
+            return None
         if last_only:
             rows, src, ldx = B, h[T - 1:], T * d
         else:
             rows, src, ldx = ntok, h, d
+        return self._sample_tail(src, ldx, rows, T, r0, b0, pos, out, last_only, advance, q8, s8, gws)
+
+    def _ragged_buffers(self) -> None:
+        """Nothing is allocated for ragged prompts until a generation uses them
+        (prefill runs outside the decode graphs, so allocating here is safe)."""
+        if self.h_last is None:
+            self.h_last = torch.zeros((self.max_batch, self.d), dtype=torch.bfloat16, device=self.device)
+            self.zero_pos = torch.zeros((self.max_batch,), dtype=torch.int32, device=self.device)
+
+    def ragged_first_token(self, b0: int, B: int, lens: torch.Tensor, out: Optional[torch.Tensor] = None):
+        """Last stage, after the last piece of a ragged prefill of cache rows
+        [b0, b0 + B) (``step(lens=...)``): the tail of a ``last_only`` prefill
+        step on the rows' kept hidden states (``h_last``: each row's own last
+        prompt position), in the same launch order: head, penalties,
+        suppression, argmax / sampler, log-probabilities, stop.  The sampler's
+        step operand is 0 for every row, what an unchunked equal-length
+        prefill passes (the positions before the prompt); the log-probability
+        record goes to history position ``lens - 1``.  Returns StageOutput."""
+        if not self.last:
+            raise ValueError("ragged_first_token: last stage only")
+        if b0 < 0 or b0 + B > self.max_batch:
+            raise ValueError("batch slice exceeds the KV cache")
+        if self.h_last is None:
+            raise ValueError("ragged_first_token: no ragged prefill piece (step(lens=...)) ran on this stage")
+        if lens.dtype != torch.int32 or lens.numel() < B or lens.device != self.h_last.device:
+            raise ValueError(f"ragged_first_token: lens must be int32 with >= {B} entries on {self.device}")
+        # prefill-shaped (T = 0 new tokens behind `lens`): scratch rows from 0, no decode workspace, no previous
+        # token counted; position lens + T - 1 takes the log-probabilities
+        return self._sample_tail(self.h_last[b0:b0 + B], self.d, B, 0, 0, b0, self.zero_pos[:B], out, True, None,
+                                 self.q8, self.s8, None, lp_pos=lens)
+
+    def _sample_tail(self, src, ldx: int, rows: int, T: int, r0: int, b0: int, pos, out, last_only: bool, advance,
+                     q8, s8, gws, lp_pos=None):
+        """The last stage's work behind its blocks on ``rows`` hidden rows
+        (``src`` with row stride ``ldx``): head, penalties, suppression, argmax
+        / sampler (step operand ``pos``), log-probabilities (at ``lp_pos`` or
+        ``pos``, plus ``T - 1``), stop."""
+        d = self.d
+        lp_pos = pos if lp_pos is None else lp_pos
         logits = self.logits[r0:r0 + rows]
         pen = self.penalties_on and last_only
         lpn = self.logprobs > 0 and last_only
@@ -681,7 +744,7 @@ class TransformerStage(StageCompute):
             if head_argmax(x_last, self.w_head, logits[:, :self.V], self.head_part[r0 * 2 * HEAD_PART_PER_ROW:], dst,
                            also, adv, hist):
                 if lpn:  # the head wrote the logits too
-                    self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
+                    self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else lp_pos, adv is not None)
                 if stp:
                     self._stop_rows(dst, b0, rows, also, hist, adv)
                 return StageOutput(logits[:, :self.V], dst)
@@ -716,7 +779,7 @@ class TransformerStage(StageCompute):
                 if pen:
                     self.pen_prev[b0:b0 + rows].copy_(nxt)
                 if lpn:
-                    self._record_logprobs(logits, nxt, b0, rows, T, pos, False)
+                    self._record_logprobs(logits, nxt, b0, rows, T, lp_pos, False)
                 if stp:
                     self._stop_rows(nxt, b0, rows, out, None, None)
                 return StageOutput(logits[:, :self.V], nxt)
@@ -727,7 +790,7 @@ class TransformerStage(StageCompute):
             if pen:
                 self.pen_prev[b0:b0 + rows].copy_(dst)
             if lpn:
-                self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
+                self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else lp_pos, adv is not None)
             if stp:
                 self._stop_rows(dst, b0, rows, also, hist, adv)
             return StageOutput(logits[:, :self.V], dst)
@@ -740,7 +803,7 @@ class TransformerStage(StageCompute):
             # decode step's penalty launch reads it from the same address on every graph replay
             self.pen_prev[b0:b0 + rows].copy_(dst)
         if lpn:
-            self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else pos, adv is not None)
+            self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else lp_pos, adv is not None)
         if stp:
             self._stop_rows(dst, b0, rows, also, hist, adv)
         return StageOutput(logits[:, :self.V], dst)

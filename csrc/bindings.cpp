@@ -285,6 +285,27 @@ PYBIND11_MODULE(_dnn_hip, m) {
     return dnn_ragged_last_rows(CP(h), ld, CIP(lens), t0, Tc, B, d, P(dst), dst_ld, ST(st));
   }, py::arg("h"), py::arg("ld"), py::arg("lens"), py::arg("t0"), py::arg("Tc"), py::arg("B"), py::arg("d"),
      py::arg("dst"), py::arg("dst_ld"), py::arg("st"));
+  m.def("logit_constraints", [](u64 x, int ld, int M, int N, u64 ctx, int ctx_ld, u64 pos, int pos_off, u64 prev,
+                                u64 bias_ids, u64 bias_vals, u64 allow, u64 bad_ids, u64 bad_len, int ngram,
+                                const std::vector<int>& h_bias_ids, const std::vector<float>& h_bias_vals,
+                                const std::vector<std::vector<int>>& h_bad, u64 st) {
+    if (h_bias_ids.size() != h_bias_vals.size()) return -1;
+    // the bad words as the [n][16] table of the C entry; an over-long one keeps its length, which the entry rejects
+    std::vector<int> flat(h_bad.size() * DNN_CON_MAX_BAD_LEN + 1, -1), lens(h_bad.size() + 1, 0);
+    for (size_t s = 0; s < h_bad.size(); ++s) {
+      lens[s] = (int)h_bad[s].size();
+      for (size_t j = 0; j < h_bad[s].size() && j < (size_t)DNN_CON_MAX_BAD_LEN; ++j)
+        flat[s * DNN_CON_MAX_BAD_LEN + j] = h_bad[s][j];
+    }
+    return dnn_logit_constraints(P(x), ld, M, N, IP(ctx), ctx_ld, CIP(pos), pos_off, CIP(prev), CIP(bias_ids),
+                                 CFP(bias_vals), (int)h_bias_ids.size(),
+                                 reinterpret_cast<const unsigned char*>(static_cast<uintptr_t>(allow)), CIP(bad_ids),
+                                 CIP(bad_len), (int)h_bad.size(), ngram, h_bias_ids.data(), h_bias_vals.data(),
+                                 flat.data(), lens.data(), ST(st));
+  }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("ctx"), py::arg("ctx_ld"), py::arg("pos"),
+     py::arg("pos_off"), py::arg("prev"), py::arg("bias_ids"), py::arg("bias_vals"), py::arg("allow"),
+     py::arg("bad_ids"), py::arg("bad_len"), py::arg("ngram"), py::arg("h_bias_ids"), py::arg("h_bias_vals"),
+     py::arg("h_bad"), py::arg("st"));
   m.def("quant_fp8_rows", [](u64 x, int ldx, u64 q, u64 scale, int M, int K, int kpad, u64 st, int split) {
     return dnn_quant_fp8_rows(CP(x), ldx, P(q), FP(scale), M, K, kpad, ST(st), split);
   }, py::arg("x"), py::arg("ldx"), py::arg("q"), py::arg("scale"), py::arg("M"), py::arg("K"), py::arg("kpad"),

@@ -174,6 +174,25 @@ int dnn_stop_rows(int* tok, int* also, int* hist, int hist_ld, const int* pos, i
                   int pad, int M, hipStream_t st);
 int dnn_stop_suppress(void* x, int ld, int M, int N, const int* state, const int* stop_ids, int n_ids, int min_new,
                       hipStream_t st);
+// logit constraints (constraints.hip, which states the semantics): logit_bias, allowed_token_ids,
+// bad_words_ids and no_repeat_ngram_size on the bf16 logits x[M][ld] (N entries used), one launch.  ctx: int32
+// [rows][ctx_ld] on the device, each row's prompt + generated tokens; len = pos[row] + pos_off (pos null:
+// pos_off).  prev (optional): prev[row] in [0, N) is stored at ctx[row, len-1] first.  The tables are DEVICE
+// arrays: bias_ids / bias_vals [n_bias] (distinct ids), allow = bitmask over [0, N) (bit i of byte i / 8; null =
+// everything allowed; (N + 7) / 8 bytes), bad_ids [n_bad][DNN_CON_MAX_BAD_LEN] with bad_len [n_bad] entries
+// used; h_* are HOST copies of the same tables, which the entry checks on every call.  -1, nothing launched:
+// null x, null ctx when ngram > 0 or a bad word is longer than one token, ld not a multiple of 8 or below N, x
+// not 16-byte aligned, a count above its cap, a bad-word length outside 1..16, ngram outside 0..16, a table id
+// outside [0, N), a non-finite bias; -2: M > 65535.  M <= 0 returns 0.
+#define DNN_CON_MAX_BIAS 256
+#define DNN_CON_MAX_BAD 64
+#define DNN_CON_MAX_BAD_LEN 16
+#define DNN_CON_MAX_NGRAM 16
+int dnn_logit_constraints(void* x, int ld, int M, int N, int* ctx, int ctx_ld, const int* pos, int pos_off,
+                          const int* prev, const int* bias_ids, const float* bias_vals, int n_bias,
+                          const unsigned char* allow, const int* bad_ids, const int* bad_len, int n_bad, int ngram,
+                          const int* h_bias_ids, const float* h_bias_vals, const int* h_bad_ids, const int* h_bad_len,
+                          hipStream_t st);
 // ragged prompts (ragged.hip): one piece of a right-padded prefill covers prompt positions [t0, t0 + Tc) of B
 // sequences, its bf16 hidden states h as rows (b * Tc + t) of ld entries.  For sequence b with q = lens[b] -
 // 1 - t0 in [0, Tc) (its own last prompt position lies in this piece) row h[(b * Tc + q) * ld : +d] is copied

@@ -90,6 +90,48 @@ int main() {
   expect_reject(dnn_ragged_last_rows(p, 16, ip, 0, 0, 2, 16, p, 16, st), "ragged Tc=0");
   expect_reject(dnn_ragged_last_rows(buf + 2, 16, ip, 0, 4, 2, 16, buf + 2, 16, st), "ragged misaligned rows");
   expect_noop(dnn_ragged_last_rows(nullptr, 16, ip, 0, 4, 0, 16, p, 16, st), "ragged B=0");
+  // logit constraints: the host copies of the tables are read in full before any launch
+  {
+    const unsigned char* mask = reinterpret_cast<const unsigned char*>(buf);
+    int ids[DNN_CON_MAX_BIAS];
+    float vals[DNN_CON_MAX_BIAS];
+    for (int k = 0; k < DNN_CON_MAX_BIAS; ++k) {
+      ids[k] = k;
+      vals[k] = 0.5f;
+    }
+    int words[DNN_CON_MAX_BAD * DNN_CON_MAX_BAD_LEN], lens[DNN_CON_MAX_BAD];
+    for (int s = 0; s < DNN_CON_MAX_BAD; ++s) {
+      lens[s] = DNN_CON_MAX_BAD_LEN;
+      for (int j = 0; j < DNN_CON_MAX_BAD_LEN; ++j) words[s * DNN_CON_MAX_BAD_LEN + j] = (s + j) % 1000;
+    }
+    const int full_b = DNN_CON_MAX_BIAS, full_w = DNN_CON_MAX_BAD;
+    auto con = [&](void* x, int ld, int M, int N, int* ctx, int ctx_ld, int n_bias, int n_bad, int ngram) {
+      return dnn_logit_constraints(x, ld, M, N, ctx, ctx_ld, ip, 0, nullptr, ip, f, n_bias, mask, ip, ip, n_bad, ngram,
+                                   ids, vals, words, lens, st);
+    };
+    expect_reject(con(nullptr, 1024, 2, 1000, ip, 16, full_b, full_w, 3), "constraints null x");
+    expect_reject(con(p, 1024, 2, 1000, nullptr, 16, full_b, full_w, 3), "constraints null ctx");
+    expect_reject(con(p, 1004, 2, 1000, ip, 16, full_b, full_w, 3), "constraints ld%8");
+    expect_reject(con(p, 992, 2, 1000, ip, 16, full_b, full_w, 3), "constraints ld < N");
+    expect_reject(con(buf + 2, 1024, 2, 1000, ip, 16, full_b, full_w, 3), "constraints misaligned rows");
+    expect_reject(con(p, 1024, 2, 1000, ip, 0, full_b, full_w, 3), "constraints ctx_ld = 0");
+    expect_reject(con(p, 1024, 2, 1000, ip, 16, full_b + 1, full_w, 3), "constraints 257 bias ids");
+    expect_reject(con(p, 1024, 2, 1000, ip, 16, full_b, full_w + 1, 3), "constraints 65 bad words");
+    expect_reject(con(p, 1024, 2, 1000, ip, 16, full_b, full_w, 17), "constraints ngram 17");
+    expect_reject(con(p, 1024, 2, 1000, ip, 16, full_b, full_w, -1), "constraints ngram -1");
+    expect_reject(con(p, 1024, 2, 200, ip, 16, full_b, 0, 0), "constraints bias id >= N");
+    expect_reject(con(p, 1024, 2, 50, ip, 16, 0, full_w, 0), "constraints bad-word id >= N");
+    lens[63] = 17;
+    expect_reject(con(p, 1024, 2, 1000, ip, 16, 0, full_w, 0), "constraints bad-word length 17");
+    lens[63] = 0;
+    expect_reject(con(p, 1024, 2, 1000, ip, 16, 0, full_w, 0), "constraints bad-word length 0");
+    lens[63] = 16;
+    vals[255] = __builtin_inff();
+    expect_reject(con(p, 1024, 2, 1000, ip, 16, full_b, 0, 0), "constraints infinite bias");
+    vals[255] = 0.5f;
+    expect_reject(con(p, 1024, 65536, 1000, ip, 16, full_b, full_w, 3), "constraints M > 65535");
+    expect_noop(con(nullptr, 1024, 0, 1000, nullptr, 16, full_b + 1, full_w, 99), "constraints M=0");
+  }
   // CIFAR
   expect_reject(dnn_cifar_set_v4_pt(3), "v4 pt%4");
   expect_reject(dnn_cifar_set_v4_pt(36), "v4 pt>32");

@@ -269,12 +269,12 @@ def build_stage(ctx: NodeContext, part: int, ranges, device: torch.device, full_
                                     repetition_penalty=pipe.repetition_penalty,
                                     presence_penalty=pipe.presence_penalty,
                                     frequency_penalty=pipe.frequency_penalty, logprobs=pipe.logprobs,
-                                    stop=pipe.stop)
+                                    stop=pipe.stop, constraints=pipe.constraints)
     else:
         st = TorchStage(pipe.model, sd, a, b, first, last, device,
                         sampling=(pipe.temperature, pipe.top_k, pipe.seed, pipe.top_p, pipe.min_p,
                                   pipe.repetition_penalty, pipe.presence_penalty, pipe.frequency_penalty,
-                                  pipe.logprobs, pipe.stop),
+                                  pipe.logprobs, pipe.stop, pipe.constraints),
                         input_dtype=pipe.input_dtype, input_table=_input_table(pipe))
     log(f"[{ctx.node_id}] Successfully loaded weights into stage {part} (layers [{a},{b}]) on {device}.")
     return st, full_sd

@@ -14,7 +14,8 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
   ``num_microbatches``, ``seq_len``, ``decode_steps``, ``prompt_len``, ``prompts``, ``temperature``, ``top_k``,
   ``top_p``, ``min_p``, ``seed``, ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``,
   ``logprobs``, ``eos_token_id``, ``stop_token_ids``, ``stop_sequences``, ``min_new_tokens``,
-  ``pad_token_id``, ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
+  ``pad_token_id``, ``logit_bias``, ``allowed_token_ids``, ``bad_words_ids``, ``no_repeat_ngram_size``,
+  ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
   ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``input_dtype``, ``input_mean``,
   ``input_std`` (CIFAR: stage 0 takes uint8 images and normalises them by table); per node
   ``layers: [start, end]`` (inclusive, as in
@@ -130,6 +131,109 @@ def make_stop(vocab: int, eos_token_id: Any = None, stop_token_ids: Any = None, 
     return StopConfig(tuple(ids), tuple(seqs), int(min_new_tokens), pad)
 
 
+# caps of the logit constraints: the tables of csrc/kernels/constraints.hip are sized by them
+CON_MAX_BIAS = 256
+CON_MAX_BAD_WORDS = 64
+CON_MAX_BAD_LEN = 16
+CON_MAX_NGRAM = 16
+CON_MAX_ABS_BIAS = 100.0
+
+
+@dataclass(frozen=True)
+class ConstraintConfig:
+    """The hard constraints on the logits of a generation (runtime/sampling.py
+    ``constraints_ref`` states the semantics): what a last stage gets when any
+    is configured."""
+
+    logit_bias: Tuple[Tuple[int, float], ...] = ()             # (id, bias), distinct ids
+    allowed_token_ids: Optional[Tuple[int, ...]] = None        # None = every id is allowed
+    bad_words_ids: Tuple[Tuple[int, ...], ...] = ()
+    no_repeat_ngram_size: int = 0
+
+    @property
+    def needs_context(self) -> bool:
+        """Does a rule read the row's ordered context (prompt + generated)?"""
+        return self.no_repeat_ngram_size > 0 or any(len(s) > 1 for s in self.bad_words_ids)
+
+
+def make_constraints(vocab: int, logit_bias: Any = None, allowed_token_ids: Any = None, bad_words_ids: Any = None,
+                     no_repeat_ngram_size: Any = 0) -> Optional[ConstraintConfig]:
+    """Validate the four constraint keys against a vocabulary of ``vocab``
+    entries.  ``logit_bias`` is an object with string or integer keys or a list
+    of ``[id, bias]`` pairs.  Returns None when every key is neutral; raises
+    ``ConfigError`` for a value out of range, a duplicate, a count above the
+    caps, or an ``allowed_token_ids`` whose every member is a one-token bad
+    word (nothing could ever be generated)."""
+    import math
+
+    def ids_of(key: str, v: Any) -> List[int]:
+        if not isinstance(v, (list, tuple)) or any(not _is_int(e) for e in v):
+            raise ConfigError(f"ERROR: '{key}' must be a list of integers, got {v!r}")
+        bad = [e for e in v if not 0 <= e < vocab]
+        if bad:
+            raise ConfigError(f"ERROR: '{key}' holds ids outside [0, {vocab}): {bad!r}")
+        return [int(e) for e in v]
+
+    bias: List[Tuple[int, float]] = []
+    if logit_bias is not None:
+        if isinstance(logit_bias, dict):
+            pairs = []
+            for k, b in logit_bias.items():
+                if isinstance(k, str):
+                    try:
+                        k = int(k.strip())
+                    except ValueError:
+                        raise ConfigError(f"ERROR: 'logit_bias' key {k!r} is no token id") from None
+                pairs.append((k, b))
+        elif isinstance(logit_bias, (list, tuple)) and all(isinstance(e, (list, tuple)) and len(e) == 2
+                                                           for e in logit_bias):
+            pairs = [(e[0], e[1]) for e in logit_bias]
+        else:
+            raise ConfigError(f"ERROR: 'logit_bias' must be an object {{id: bias}} or a list of [id, bias] pairs, "
+                              f"got {logit_bias!r}")
+        for k, b in pairs:
+            if not _is_int(k) or not 0 <= k < vocab:
+                raise ConfigError(f"ERROR: 'logit_bias' id {k!r} outside [0, {vocab})")
+            if isinstance(b, bool) or not isinstance(b, (int, float)) or not math.isfinite(b) \
+                    or abs(b) > CON_MAX_ABS_BIAS:
+                raise ConfigError(f"ERROR: 'logit_bias' of id {k} must be a finite number with |b| <= "
+                                  f"{CON_MAX_ABS_BIAS:g}, got {b!r}")
+            bias.append((int(k), float(b)))
+        if len({k for k, _ in bias}) != len(bias):
+            raise ConfigError(f"ERROR: the ids of 'logit_bias' must be distinct, got {[k for k, _ in bias]!r}")
+        if len(bias) > CON_MAX_BIAS:
+            raise ConfigError(f"ERROR: at most {CON_MAX_BIAS} ids in 'logit_bias', got {len(bias)}")
+    allowed = None
+    if allowed_token_ids is not None:
+        allowed = ids_of("allowed_token_ids", allowed_token_ids)
+        if not allowed:
+            raise ConfigError("ERROR: 'allowed_token_ids' must not be empty (leave the key out to allow every id)")
+        if len(set(allowed)) != len(allowed):
+            raise ConfigError("ERROR: the ids of 'allowed_token_ids' must be distinct")
+    words_in = [] if bad_words_ids is None else bad_words_ids
+    if not isinstance(words_in, (list, tuple)) or any(not isinstance(q, (list, tuple)) for q in words_in):
+        raise ConfigError(f"ERROR: 'bad_words_ids' must be a list of lists of integers, got {bad_words_ids!r}")
+    if len(words_in) > CON_MAX_BAD_WORDS:
+        raise ConfigError(f"ERROR: at most {CON_MAX_BAD_WORDS} 'bad_words_ids', got {len(words_in)}")
+    words = []
+    for q in words_in:
+        if not 1 <= len(q) <= CON_MAX_BAD_LEN:
+            raise ConfigError(f"ERROR: every entry of 'bad_words_ids' holds 1..{CON_MAX_BAD_LEN} ids, got {len(q)}")
+        words.append(tuple(ids_of("bad_words_ids", q)))
+    n = no_repeat_ngram_size
+    if not _is_int(n) or not 0 <= n <= CON_MAX_NGRAM:
+        raise ConfigError(f"ERROR: 'no_repeat_ngram_size' must be an integer in [0, {CON_MAX_NGRAM}], got {n!r}")
+    if allowed is not None and set(allowed) <= {w[0] for w in words if len(w) == 1}:
+        raise ConfigError("ERROR: every id of 'allowed_token_ids' is also a one-token entry of 'bad_words_ids': "
+                          "nothing could be generated")
+    if not bias and allowed is None and not words and n == 0:
+        return None
+    return ConstraintConfig(tuple(bias), None if allowed is None else tuple(allowed), tuple(words), int(n))
+
+
+CONSTRAINT_KEYS = ("logit_bias", "allowed_token_ids", "bad_words_ids", "no_repeat_ngram_size")
+
+
 def make_prompt_lists(vocab: int, prompts: Any, n_seq: int, key: str = "prompts") -> Tuple[Tuple[int, ...], ...]:
     """Validate the prompts of one generation (config key ``prompts``, or the
     parsed ``--prompt``): a list of 1..``n_seq`` non-empty lists of ids in
@@ -183,6 +287,7 @@ class PipelineConfig:
     frequency_penalty: float = 0.0            # subtracted per time the token was generated (0 = off)
     logprobs: int = 0                         # 1..20: record each token's log-probability and the top-n (0 = off)
     stop: Optional[StopConfig] = None         # stop ids / sequences, min_new_tokens, pad_token_id (None = never stops)
+    constraints: Optional[ConstraintConfig] = None  # logit_bias, allowed / bad ids, no_repeat_ngram_size (None = off)
     rpc_timeout_s: Optional[float] = None     # per-hop SendTensor deadline (reference: none)
     health_timeout_s: float = 120.0           # readiness barrier before stage 0 sends
     comm_timeout_s: float = 300.0             # process-group (RCCL/gloo) op timeout
@@ -351,6 +456,15 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         from .models import model_info  # the vocabulary (imports torch: only when a stop key is present)
         stop = make_stop(model_info(model).cfg.vocab_size, **{k: cfg.get(k) for k in STOP_KEYS if k != "min_new_tokens"},
                          min_new_tokens=cfg.get("min_new_tokens", 0))
+    cons = None
+    if any(cfg.get(k) is not None for k in CONSTRAINT_KEYS):
+        if model == "cifar10":
+            raise ConfigError(f"ERROR: {[k for k in CONSTRAINT_KEYS if cfg.get(k) is not None]!r} exist for the "
+                              f"generating models only, got model '{model}'")
+        from .models import model_info  # the vocabulary (imports torch: only when a constraint key is present)
+        cons = make_constraints(model_info(model).cfg.vocab_size,
+                                **{k: cfg.get(k) for k in CONSTRAINT_KEYS if k != "no_repeat_ngram_size"},
+                                no_repeat_ngram_size=cfg.get("no_repeat_ngram_size", 0))
     if model == "cifar10":
         for key, v, neutral in (("repetition_penalty", rp, 1), ("presence_penalty", pens["presence_penalty"], 0),
                                 ("frequency_penalty", pens["frequency_penalty"], 0)):
@@ -392,7 +506,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         prefill_chunk=int(cfg.get("prefill_chunk", 0)),
         temperature=float(cfg.get("temperature", 0.0)), top_k=int(cfg.get("top_k", 0)), seed=int(cfg.get("seed", 0)),
         top_p=float(tp), min_p=float(mp), repetition_penalty=float(rp), presence_penalty=pens["presence_penalty"],
-        frequency_penalty=pens["frequency_penalty"], logprobs=nlp, stop=stop,
+        frequency_penalty=pens["frequency_penalty"], logprobs=nlp, stop=stop, constraints=cons,
         rpc_timeout_s=cfg.get("rpc_timeout_s"), health_timeout_s=float(cfg.get("health_timeout_s", 120.0)),
         comm_timeout_s=float(cfg.get("comm_timeout_s", 300.0)),
         heartbeat_timeout_s=float(cfg.get("heartbeat_timeout_s", 15.0)),

@@ -8,7 +8,8 @@ from typing import Optional
 
 import torch
 
-from ..config import LOGPROBS_MAX_N, STOP_MAX_IDS, STOP_MAX_SEQ_LEN, STOP_MAX_SEQS
+from ..config import (CON_MAX_BAD_LEN, CON_MAX_BAD_WORDS, CON_MAX_BIAS, CON_MAX_NGRAM, LOGPROBS_MAX_N, STOP_MAX_IDS,
+                      STOP_MAX_SEQ_LEN, STOP_MAX_SEQS)
 
 STOP_STATE_WORDS = 18  # csrc/kernels/api.h DNN_STOP_STATE_WORDS
 from ._lib import check, lib, ptr, stream_ptr
@@ -547,3 +548,103 @@ def ragged_last_rows(h: torch.Tensor, lens: torch.Tensor, t0: int, Tc: int, B: i
     check(lib().ragged_last_rows(h=ptr(h), ld=ld, lens=ptr(lens), t0=t0, Tc=Tc, B=B, d=d, dst=ptr(dst),
                                  dst_ld=dst_ld, st=stream_ptr()), "ragged_last_rows")
     return dst
+
+
+class ConstraintTables:
+    """The device tables of ``dnn_logit_constraints`` (constraints.hip) for one
+    ``config.ConstraintConfig`` and vocabulary, built once (``constraint_tables``):
+    bias ids (int32) and values (fp32), the allowed-id bitmask over ``[0, n_vocab)``
+    (uint8, bit ``i % 8`` of byte ``i // 8``; None = everything allowed), the bad
+    words as int32 (n, 16) with their lengths, and ``no_repeat_ngram_size``.  The
+    host copies travel with every launch, where the entry point checks them."""
+
+    __slots__ = ("n_vocab", "device", "bias_ids", "bias_vals", "allow", "bad_ids", "bad_len", "ngram", "h_bias_ids",
+                 "h_bias_vals", "h_bad", "needs_context")
+
+
+def constraint_tables(cons, n_vocab: int, device) -> ConstraintTables:
+    """Validate ``cons`` (``config.ConstraintConfig``) against ``n_vocab`` and the
+    caps, and put its tables on ``device``."""
+    n_vocab = int(n_vocab)
+    ids = [int(k) for k, _ in cons.logit_bias]
+    vals = [float(v) for _, v in cons.logit_bias]
+    words = [[int(e) for e in s] for s in cons.bad_words_ids]
+    allowed = None if cons.allowed_token_ids is None else [int(i) for i in cons.allowed_token_ids]
+    ngram = int(cons.no_repeat_ngram_size)
+    if len(ids) > CON_MAX_BIAS or len(words) > CON_MAX_BAD_WORDS:
+        raise ValueError(f"constraint_tables: at most {CON_MAX_BIAS} bias ids and {CON_MAX_BAD_WORDS} bad words, got "
+                         f"{len(ids)} and {len(words)}")
+    if any(not 1 <= len(s) <= CON_MAX_BAD_LEN for s in words):
+        raise ValueError(f"constraint_tables: a bad word holds 1..{CON_MAX_BAD_LEN} ids")
+    if not 0 <= ngram <= CON_MAX_NGRAM:
+        raise ValueError(f"constraint_tables: no_repeat_ngram_size {ngram} outside [0, {CON_MAX_NGRAM}]")
+    bad = [i for i in ids + [e for s in words for e in s] + (allowed or []) if not 0 <= i < n_vocab]
+    if bad:
+        raise ValueError(f"constraint_tables: ids outside [0, {n_vocab}): {bad!r}")
+    if len(set(ids)) != len(ids):
+        raise ValueError("constraint_tables: the bias ids must be distinct")
+    if any(not math.isfinite(v) for v in vals):
+        raise ValueError("constraint_tables: a bias must be finite")
+    if allowed is not None and not allowed:
+        raise ValueError("constraint_tables: allowed_token_ids must not be empty")
+    t = ConstraintTables()
+    t.n_vocab, t.device, t.ngram = n_vocab, torch.device(device), ngram
+    t.h_bias_ids, t.h_bias_vals, t.h_bad = ids, vals, words
+    t.needs_context = ngram > 0 or any(len(s) > 1 for s in words)
+    t.bias_ids = torch.tensor(ids, dtype=torch.int32, device=device) if ids else None
+    t.bias_vals = torch.tensor(vals, dtype=torch.float32, device=device) if ids else None
+    t.allow = None
+    if allowed is not None:
+        bits = torch.zeros((-(-n_vocab // 8) * 8,), dtype=torch.uint8)
+        bits[torch.tensor(allowed, dtype=torch.int64)] = 1
+        weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32)
+        t.allow = (bits.view(-1, 8).to(torch.int32) * weights).sum(1).to(torch.uint8).to(device)
+    t.bad_ids = t.bad_len = None
+    if words:
+        flat = torch.full((len(words), CON_MAX_BAD_LEN), -1, dtype=torch.int32)
+        for s, w in enumerate(words):
+            flat[s, :len(w)] = torch.tensor(w, dtype=torch.int32)
+        t.bad_ids = flat.to(device)
+        t.bad_len = torch.tensor([len(w) for w in words], dtype=torch.int32, device=device)
+    return t
+
+
+def logit_constraints(logits: torch.Tensor, n_vocab: int, tables: ConstraintTables,
+                      ctx: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None, pos_off: int = 0,
+                      prev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """logit_bias, allowed_token_ids, bad_words_ids and no_repeat_ngram_size in
+    place on the first ``n_vocab`` entries of every row of bf16 ``logits``, one
+    launch (constraints.hip; ``runtime/sampling.constraints_ref`` is the bitwise
+    mirror and states the rules).  ``ctx`` (int32 (>= M, L), contiguous rows):
+    each row's prompt + generated tokens, of which ``pos[row] + pos_off``
+    (``pos`` None: ``pos_off``) are valid; needed when ``tables.needs_context``.
+    ``prev`` (int32 per row, or None): the token each row generated last, stored
+    as the newest context entry first (-1 / out-of-range: nothing stored)."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("logit_constraints: bf16 (M, >= n_vocab) logits with contiguous rows expected")
+    M = logits.shape[0]
+    if not 0 < n_vocab <= logits.shape[1] or int(n_vocab) != tables.n_vocab:
+        raise ValueError(f"logit_constraints: n_vocab = {n_vocab} outside the row width {logits.shape[1]} or not the "
+                         f"tables' {tables.n_vocab}")
+    ld = logits.stride(0) if M > 1 else logits.shape[1]
+    if ld % 8 or ld < n_vocab or logits.data_ptr() % 16:
+        raise ValueError("logit_constraints: rows must start 16-byte aligned (row stride a multiple of 8, >= n_vocab)")
+    ctx_ld = 0
+    if ctx is not None:
+        if ctx.dtype != torch.int32 or ctx.dim() != 2 or ctx.shape[0] < M or ctx.stride(1) != 1:
+            raise ValueError(f"logit_constraints: ctx must be int32 (>= {M}, L) with contiguous rows")
+        ctx_ld = ctx.stride(0) if ctx.shape[0] > 1 else ctx.shape[1]
+        if ctx_ld < ctx.shape[1]:
+            raise ValueError("logit_constraints: overlapping ctx rows")
+    elif tables.needs_context:
+        raise ValueError("logit_constraints: these constraints need the context table ctx")
+    for t, nm in ((pos, "pos"), (prev, "prev")):
+        if t is not None and (t.dtype != torch.int32 or t.numel() < M or not t.is_contiguous()):
+            raise ValueError(f"logit_constraints: {nm} must be contiguous int32 with >= {M} entries")
+    check(lib().logit_constraints(x=ptr(logits), ld=ld, M=M, N=int(n_vocab), ctx=ptr(ctx), ctx_ld=ctx_ld, pos=ptr(pos),
+                                  pos_off=int(pos_off), prev=ptr(prev if ctx is not None else None),
+                                  bias_ids=ptr(tables.bias_ids), bias_vals=ptr(tables.bias_vals), allow=ptr(tables.allow),
+                                  bad_ids=ptr(tables.bad_ids), bad_len=ptr(tables.bad_len), ngram=tables.ngram,
+                                  h_bias_ids=tables.h_bias_ids, h_bias_vals=tables.h_bias_vals, h_bad=tables.h_bad,
+                                  st=stream_ptr()), "logit_constraints")
+    return logits

@@ -105,6 +105,14 @@ def penalties_on(pipe) -> bool:
     return pipe.repetition_penalty != 1.0 or pipe.presence_penalty != 0.0 or pipe.frequency_penalty != 0.0
 
 
+def needs_prompt_ids(pipe) -> bool:
+    """The last stage needs every prompt's token ids: for the penalties, or for
+    logit constraints that read the rows' context (``no_repeat_ngram_size``, a
+    bad word longer than one token)."""
+    cons = getattr(pipe, "constraints", None)
+    return penalties_on(pipe) or (cons is not None and cons.needs_context)
+
+
 def _sync(dev):
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
@@ -240,7 +248,7 @@ def run_generate_dist(ctx, args, stage, info, progress=None) -> int:
     if links.nxt is not None:
         links.nxt.send_header(kind, B, T, steps)
     check_capacity([stage], *kv_capacity(pipe, T))
-    ring = DecodeRing([stage], links, S, M, B, progress=progress, forward_prompt_ids=penalties_on(pipe),
+    ring = DecodeRing([stage], links, S, M, B, progress=progress, forward_prompt_ids=needs_prompt_ids(pipe),
                       ragged=kind == KIND_RAGGED)
     pf, dec, steps = _timed_generate(ring, prompts, T, steps, dev, pipe.prefill_chunk, mlens)
     if r == 0:

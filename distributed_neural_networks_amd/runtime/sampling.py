@@ -307,6 +307,92 @@ def stop_suppress_ref(logits: torch.Tensor, state: torch.Tensor, stop_ids, min_n
     return x
 
 
+# ---------------------------------------------------------------------- logit constraints
+def constraints_store_prev(ctx: torch.Tensor, lens, prev, vocab: int) -> torch.Tensor:
+    """A copy of the context table ``ctx`` (M, L) in which row ``r`` holds
+    ``prev[r]`` at ``lens[r] - 1`` when ``prev[r]`` lies in ``[0, vocab)`` and
+    ``1 <= lens[r] <= L``: the previous step's token becomes the newest entry
+    of the row's context (what ``dnn_logit_constraints`` stores first)."""
+    c = ctx.detach().to(device="cpu", dtype=torch.int32).clone()
+    ls = [int(v) for v in torch.as_tensor(lens).reshape(-1).tolist()]
+    ps = [int(v) for v in torch.as_tensor(prev).reshape(-1).tolist()]
+    for r in range(c.shape[0]):
+        if 0 <= ps[r] < int(vocab) and 1 <= ls[r] <= c.shape[1]:
+            c[r, ls[r] - 1] = ps[r]
+    return c
+
+
+def constraints_ref(logits: torch.Tensor, cons, ctx: Optional[torch.Tensor] = None, lens=None,
+                    prev=None) -> torch.Tensor:
+    """The hard constraints on one step's logits: the torch mirror of
+    ``dnn_logit_constraints`` (csrc/kernels/constraints.hip), bitwise equal to
+    it, and the one written definition.
+
+    A row's context is ``c[0..len)``: its own prompt tokens, then its generated
+    tokens in order (``ctx[row, :len]``; pads are never part of it, a ragged
+    row's context starts at its own length).  The rules run after the penalties
+    and before the ``min_new_tokens`` suppression and the argmax / sampler, per
+    row in this order:
+
+    1. ``logit_bias`` ``{id: b}``: ``x[id] = bf16(float(x[id]) + b)``, one fp32
+       add rounded to nearest even.  Entries not listed keep their bits.
+    2. ``allowed_token_ids``: every entry of ``[0, V)`` not in the list becomes
+       bf16 ``-inf``.
+    3. ``bad_words_ids``: for each sequence ``s`` of length ``L``, when
+       ``len >= L - 1`` and ``c[len-L+1 .. len) == s[0 .. L-1)``, the entry
+       ``s[L-1]`` becomes ``-inf``.  A one-token sequence is banned at every
+       step; prompt tokens take part in the match.
+    4. ``no_repeat_ngram_size`` = n: for every ``j`` with ``0 <= j`` and
+       ``j + n - 1 <= len - 1``, when ``c[j .. j+n-1) == c[len-n+1 .. len)``, the
+       entry ``c[j+n-1]`` becomes ``-inf``.  ``n = 1`` bans every token of the
+       context, a row with ``len < n`` bans nothing, and the suffix never
+       matches itself (the token behind it does not exist yet).
+
+    A ban wins over a bias on the same entry.  Context ids outside ``[0, V)``
+    are compared but never used as an index.
+
+    ``logits`` (M, V) (rounded to bf16 first); ``cons`` a
+    ``config.ConstraintConfig``; ``ctx`` int (M, L) and ``lens`` (M,) ints (only
+    read by rules 3 and 4; ``lens[r]`` outside ``[0, L]`` is clamped); ``prev``
+    (M,) ints: ``constraints_store_prev`` first.  Returns bf16 on the CPU."""
+    x = logits.detach().to(device="cpu", dtype=torch.bfloat16).clone()
+    M, V = x.shape
+    neg = float("-inf")
+    if cons.logit_bias:
+        ids = torch.tensor([k for k, _ in cons.logit_bias], dtype=torch.int64)
+        b = torch.tensor([v for _, v in cons.logit_bias], dtype=torch.float32)
+        x[:, ids] = (x[:, ids].to(torch.float32) + b[None, :]).to(torch.bfloat16)
+    if cons.allowed_token_ids is not None:
+        keep = torch.zeros((V,), dtype=torch.bool)
+        keep[torch.tensor(list(cons.allowed_token_ids), dtype=torch.int64)] = True
+        x[:, ~keep] = neg
+    n = int(cons.no_repeat_ngram_size)
+    if not cons.needs_context:
+        for s in cons.bad_words_ids:
+            x[:, int(s[0])] = neg
+        return x
+    if ctx is None or lens is None:
+        raise ValueError("constraints_ref: bad words longer than one token and no_repeat_ngram_size need ctx and lens")
+    c_all = ctx.detach().to(device="cpu", dtype=torch.int64)
+    ls = [int(v) for v in torch.as_tensor(lens).reshape(-1).tolist()]
+    if prev is not None:
+        c_all = constraints_store_prev(c_all, ls, prev, V).to(torch.int64)
+    for r in range(M):
+        ln = min(max(ls[r], 0), c_all.shape[1])
+        c = c_all[r, :ln]
+        for s in cons.bad_words_ids:
+            L = len(s)
+            if ln >= L - 1 and (L == 1 or bool((c[ln - L + 1:] == torch.tensor(s[:-1], dtype=torch.int64)).all())):
+                x[r, int(s[-1])] = neg
+        if n > 0 and ln >= n:
+            w = c.unfold(0, n, 1)  # window j = c[j .. j+n): ln - n + 1 of them
+            hit = (w[:, :n - 1] == c[ln - n + 1:][None, :]).all(1)
+            t = w[hit, n - 1]
+            t = t[(t >= 0) & (t < V)]
+            x[r, t] = neg
+    return x
+
+
 # ---------------------------------------------------------------------- ragged prompts
 def ragged_last_rows_ref(h: torch.Tensor, lens: torch.Tensor, t0: int, Tc: int, B: int, d: int,
                          dst: torch.Tensor) -> torch.Tensor:

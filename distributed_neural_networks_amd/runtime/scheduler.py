@@ -326,7 +326,10 @@ class DecodeRing:
         (``penalties_on``) needs the prompt's token ids, which only group 0
         has, so before a microbatch's first prefill piece rank 0 sends its
         (B, T) int32 ids down the stage links, the middle ranks pass them on
-        and the last rank marks them (``penalty_begin``).
+        and the last rank marks them (``penalty_begin``).  A last stage whose
+        logit constraints read the rows' context (``constraints_need_context``:
+        ``no_repeat_ngram_size``, a bad word longer than one token) needs them
+        in the same way (``constraint_begin``).
 
         ``ragged`` (more than one group; every rank passes the same value, like
         ``forward_prompt_ids``): the prompts of this ring's generations come
@@ -416,6 +419,15 @@ class DecodeRing:
         if self.pen is not None and n_groups > 1 and not self.forward_prompt_ids:
             raise ValueError("a last stage with penalties on a ring of several groups needs forward_prompt_ids=True "
                              "on every rank (the prompt ids live on group 0)")
+        # last stage whose logit constraints read every row's ordered context (prompt + generated): the context
+        # starts as the prompt (_prefill: constraint_begin), forgets the discarded sample of a non-final prefill
+        # piece and keeps its previous-token entries over the capture runs (capture)
+        self.con = (self.stages[-1] if self.last and getattr(self.stages[-1], "constraints_need_context", False)
+                    else None)
+        if self.con is not None and n_groups > 1 and not self.forward_prompt_ids:
+            raise ValueError("a last stage whose constraints need the context (no_repeat_ngram_size, bad words longer "
+                             "than one token) on a ring of several groups needs forward_prompt_ids=True on every rank "
+                             "(the prompt ids live on group 0)")
         # last stage with log-probabilities (its ``logprobs`` = n >= 1): per-microbatch device histories
         # indexed by position like ``hist``, written by the stage's own launch behind the argmax / sampler
         # (``bind_logprobs``): lp_chosen[m][b, p] and lp_top_ids / lp_top_lps[m][b, p, :n] belong to the token
@@ -633,6 +645,8 @@ class DecodeRing:
                 # the whole prompt is marked before its first token is sampled (chunked prefill and the
                 # fp8-KV calibration prefills included: each starts from the prompt alone)
                 self.pen.penalty_begin(m * B, ids, lens=ln)
+            if self.con is not None:
+                self.con.constraint_begin(m * B, ids, lens=ln)  # the rows' context starts as their own prompt
             self._out_ready(m)
             for t0, Tc in pieces:
                 final = t0 + Tc == Tm
@@ -657,6 +671,8 @@ class DecodeRing:
                         self.pen.penalty_forget(m * B, B)  # this piece's sample is discarded, never counted
                     if self.stp is not None:
                         self.stp.stop_forget(m * B, B)  # ... and neither counted nor matched as a generated token
+                    if self.con is not None:
+                        self.con.constraint_forget(m * B, B)  # ... and never enters the context
                 if not self.last:
                     pf_work[k] = self.links.nxt.isend(out_pf[k][:B * Tc])
                     n_sent += 1
@@ -694,6 +710,7 @@ class DecodeRing:
             cur = self.cur[m].clone() if self.first else None
             pen = self.pen.penalty_snapshot(m * self.B, self.B) if self.pen is not None else None
             stp = self.stp.stop_snapshot(m * self.B, self.B) if self.stp is not None else None
+            con = self.con.constraint_snapshot(m * self.B, self.B) if self.con is not None else None
             self._out_ready(m)
             self.graphs[m] = GraphedStep(lambda m=m: self._decode_body(m), self.dev, warmup=1)
             self.pos[m].copy_(snap)  # the warmup/capture runs advanced the position
@@ -703,6 +720,8 @@ class DecodeRing:
                 self.pen.penalty_restore(pen)  # ... counted their tokens and overwrote the previous-token entries
             if stp is not None:
                 self.stp.stop_restore(stp)  # ... counted and matched them (a row may even have finished)
+            if con is not None:
+                self.con.constraint_restore(con)  # ... and appended them to the context (see constraint_snapshot)
         torch.cuda.synchronize(self.dev)
         self._capture_multi_step()
 
@@ -722,6 +741,8 @@ class DecodeRing:
                if self.pen is not None else None)
         stp = ([self.stp.stop_snapshot(m * self.B, self.B) for m in range(self.M)]
                if self.stp is not None else None)
+        con = ([self.con.constraint_snapshot(m * self.B, self.B) for m in range(self.M)]
+               if self.con is not None else None)
 
         def body():
             for _ in range(K):
@@ -737,6 +758,8 @@ class DecodeRing:
                     self.pen.penalty_restore(pen[m])
                 if stp is not None:
                     self.stp.stop_restore(stp[m])
+                if con is not None:
+                    self.con.constraint_restore(con[m])
         self.graph_k = GraphedStep(body, self.dev, warmup=1, reset=reset)
         self.graph_k_steps = K
         reset()  # the capture run advanced them again

@@ -167,9 +167,9 @@ class TorchStage(StageCompute):
                  device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0), input_dtype: str = "fp32", input_table=None):
         from ..models import build_golden_stage
         # sampling = (temperature, top_k, seed[, top_p, min_p[, repetition, presence, frequency penalty[, logprobs
-        #             [, stop (config.StopConfig or None)]]]])
-        if len(sampling) not in (3, 5, 8, 9, 10):
-            raise ValueError(f"sampling: 3, 5, 8, 9 or 10 entries expected, got {len(sampling)}")
+        #             [, stop (config.StopConfig or None)[, constraints (config.ConstraintConfig or None)]]]]])
+        if len(sampling) not in (3, 5, 8, 9, 10, 11):
+            raise ValueError(f"sampling: 3, 5, 8, 9, 10 or 11 entries expected, got {len(sampling)}")
         self.temperature, self.top_k, self.seed = float(sampling[0]), int(sampling[1]), int(sampling[2])
         self.top_p, self.min_p = (float(sampling[3]), float(sampling[4])) if len(sampling) >= 5 else (1.0, 0.0)
         self.rep_pen, self.pres_pen, self.freq_pen = ((float(sampling[5]), float(sampling[6]), float(sampling[7]))
@@ -183,8 +183,13 @@ class TorchStage(StageCompute):
         self.logprobs = nlp if last else 0
         self._lp_hist: Dict[int, tuple] = {}
         # stop conditions (last stage): the mirror's state (runtime/sampling.py stop_ref) per microbatch offset
-        self.stop = sampling[9] if len(sampling) == 10 and last else None
+        self.stop = sampling[9] if len(sampling) >= 10 and last else None
         self._stop_st: Dict[int, torch.Tensor] = {}
+        # logit constraints (last stage): through the mirror (runtime/sampling.py constraints_ref); per microbatch
+        # offset the rows' contexts (prompt, then generated tokens, as lists) and the token generated last
+        self.constraints = sampling[10] if len(sampling) == 11 and last else None
+        self._con_ctx: Dict[int, list] = {}
+        self._con_prev: Dict[int, Optional[torch.Tensor]] = {}
         import math
         if not (self.rep_pen > 0 and math.isfinite(self.rep_pen)):
             raise ValueError(f"repetition penalty must be a finite number > 0, got {sampling[5]!r}")
@@ -266,6 +271,31 @@ class TorchStage(StageCompute):
     def penalty_forget(self, b0: int, B: int) -> None:
         """The sample of a prefill piece before the last one is no generated token."""
         self._pen_prev[b0] = None
+
+    @property
+    def constraints_need_context(self) -> bool:
+        return self.constraints is not None and self.constraints.needs_context
+
+    def constraint_begin(self, b0: int, ids: torch.Tensor, lens=None) -> None:
+        """Start a generation on cache rows [b0, b0 + B): each row's context is
+        its own prompt (``TransformerStage.constraint_begin``)."""
+        if not self.constraints_need_context:
+            raise ValueError("constraint_begin: this stage keeps no context")
+        B, T = ids.shape
+        ls = [T] * B if lens is None else [int(v) for v in torch.as_tensor(lens).reshape(-1).tolist()]
+        self._con_ctx[b0] = [[int(v) for v in ids[b, :ls[b]].tolist()] for b in range(B)]
+        self._con_prev[b0] = None
+
+    def constraint_forget(self, b0: int, B: int) -> None:
+        """The sample of a prefill piece before the last one is no generated token."""
+        self._con_prev[b0] = None
+
+    def constraint_snapshot(self, b0: int, B: int):
+        return b0, B, [list(c) for c in self._con_ctx[b0]], self._con_prev[b0]
+
+    def constraint_restore(self, snap) -> None:
+        self._con_ctx[snap[0]] = [list(c) for c in snap[2]]
+        self._con_prev[snap[0]] = snap[3]
 
     def stop_begin(self, b0: int, B: int) -> None:
         """Start a generation on cache rows [b0, b0 + B) (``TransformerStage.stop_begin``)."""
@@ -391,8 +421,9 @@ class TorchStage(StageCompute):
 
     def _tail(self, y, b0: int, B: int, T: int, step, lp_q, out, last_only: bool):
         """What the last stage does with its head's output ``y`` (B, 1 or T, V):
-        penalties, suppression, pick, log-probabilities (row b at history
-        position ``lp_q[b]``), stop conditions.  ``T == 1`` marks a decode step
+        penalties, constraints (row b's context holds ``lp_q[b] + 1`` tokens),
+        suppression, pick, log-probabilities (row b at history position
+        ``lp_q[b]``), stop conditions.  ``T == 1`` marks a decode step
         (it counts the rows' previous token)."""
         from .sampling import pick
         logits = y[:, -1, :] if last_only else y.reshape(y.shape[0] * y.shape[1], -1)
@@ -405,6 +436,22 @@ class TorchStage(StageCompute):
             if T == 1 and self._pen_prev[b0] is not None:
                 self._pen[b0] = penalty_count(self._pen[b0], self._pen_prev[b0])
             logits = apply_penalties_ref(logits, self._pen[b0], self.rep_pen, self.freq_pen, self.pres_pen)
+            y = logits[:, None, :]
+        con = self.constraints is not None and last_only
+        if con:
+            from .sampling import constraints_ref
+            ctx = lens = None
+            if self.constraints.needs_context:
+                if b0 not in self._con_ctx or len(self._con_ctx[b0]) != B:
+                    raise ValueError(f"constraints: no constraint_begin for the {B} cache rows at {b0}")
+                rows = self._con_ctx[b0]
+                if T == 1 and self._con_prev[b0] is not None:  # a decode step appends the rows' previous token
+                    for b, t in enumerate(self._con_prev[b0].tolist()):
+                        rows[b].append(int(t))
+                lens = [q + 1 for q in lp_q]
+                width = max(max(lens), max(len(r) for r in rows), 1)
+                ctx = torch.tensor([r + [-1] * (width - len(r)) for r in rows], dtype=torch.int32)
+            logits = constraints_ref(logits, self.constraints, ctx, lens)
             y = logits[:, None, :]
         stp = self.stop is not None and last_only
         if stp:
@@ -419,6 +466,8 @@ class TorchStage(StageCompute):
                     min_p=self.min_p).to(torch.int32)
         if self.penalties_on and last_only:
             self._pen_prev[b0] = pred.clone()
+        if con and self.constraints.needs_context:
+            self._con_prev[b0] = pred.clone()
         if self.logprobs and last_only:
             from .sampling import logprobs_ref
             if b0 not in self._lp_hist:

@@ -84,7 +84,8 @@ class TransformerStage(StageCompute):
                  fp8: bool = False, temperature: float = 0.0, top_k: int = 0, seed: int = 0,
                  kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
                  top_p: float = 1.0, min_p: float = 0.0, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0, stop=None):
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0, stop=None,
+                 constraints=None):
         info = model_info(model)
         # fp8 weights, prefill (W8A8) activations: "e4m3" (default) = one e4m3
         # byte per activation, per-row scale, at the fp8 MFMA rate; "split" =
@@ -136,6 +137,11 @@ class TransformerStage(StageCompute):
                    + (self.stop.pad_token_id,) if not 0 <= i < V]
             if bad:
                 raise ValueError(f"stop: ids outside [0, {V}): {bad!r}")
+        # logit constraints (last stage; config.ConstraintConfig or None): logit_bias, allowed_token_ids,
+        # bad_words_ids and no_repeat_ngram_size, one launch of its own between the penalty launch and the
+        # suppression / argmax / sampler launches (csrc/kernels/constraints.hip); None = nothing allocated,
+        # nothing launched
+        self.constraints = constraints if last else None
         self.model, self.family, self.cfg = model, info.family, info.cfg
         self.start, self.end, self.first, self.last = start, end, first, last
         self.device = dev = torch.device(device)
@@ -405,13 +411,25 @@ class TransformerStage(StageCompute):
             self.buf_lnf = torch.empty((ntok, d), dtype=bf, device=dev)
             self.logits = torch.empty((ntok, self.Vpad), dtype=bf, device=dev)
             self.next_ids = torch.empty((ntok,), dtype=torch.int32, device=dev)
+        # logit constraints: the device tables, built once, and (only for no_repeat_ngram_size or a bad word
+        # longer than one token) every KV row's ordered context: its prompt, then its generated tokens
+        self.con_tables = self.con_ctx = None
+        if self.constraints is not None:
+            self.con_tables = T_.constraint_tables(self.constraints, self.V, dev)  # ValueError: ids, caps
+            if self.con_tables.needs_context:
+                self.con_ctx = torch.full((self.max_batch, self.max_seq), -1, dtype=torch.int32, device=dev)
         self.pen_state = self.pen_prev = None
+        if self.con_ctx is not None:
+            # the token each row generated last, which the next decode step's constraint launch appends to the
+            # row's context: the same entry the penalty launch counts, so one copy per step serves both
+            self.pen_prev = torch.full((self.max_batch,), -1, dtype=torch.int32, device=dev)
         if self.penalties_on:
             # per KV row: the uint16 state of every vocabulary entry (bit 15 = in the prompt, bits 0..14 =
             # times generated) and the token the row generated last (-1: none yet), which the next decode
             # step's penalty launch counts
             self.pen_state = torch.zeros((self.max_batch, self.Vpad), dtype=torch.int16, device=dev)
-            self.pen_prev = torch.full((self.max_batch,), -1, dtype=torch.int32, device=dev)
+            if self.pen_prev is None:
+                self.pen_prev = torch.full((self.max_batch,), -1, dtype=torch.int32, device=dev)
 
         # log-probabilities: the kernel's workspace (arrival counters, which it leaves at zero, and one
         # launch's per-chunk partials) and the histories bound per microbatch (bind_logprobs)
@@ -422,6 +440,58 @@ class TransformerStage(StageCompute):
 
         # stop conditions: g, the finish record and the window of every KV row
         self.stop_state = T_.stop_state(self.max_batch, dev) if self.stop is not None else None
+
+    # ------------------------------------------------------------------ logit constraints
+    @property
+    def constraints_need_context(self) -> bool:
+        """Does this stage keep every row's ordered context (``constraint_begin``
+        must then give it each prompt's token ids)?"""
+        return self.con_ctx is not None
+
+    def constraint_begin(self, b0: int, ids: torch.Tensor, lens: Optional[torch.Tensor] = None) -> None:
+        """Start a generation on cache rows [b0, b0 + B): the (B, T) prompt
+        ``ids`` becomes the rows' context; with ``lens`` (ragged prompts) row b's
+        context is ``ids[b, :lens[b]]`` (the pads behind it are written too, but
+        they lie at and beyond the row's length, where every decode step stores
+        its token before any scan reads the entry).  Before the prompt's first
+        prefill piece; no previous token yet."""
+        if self.con_ctx is None:
+            raise ValueError("constraint_begin: this stage keeps no context (no no_repeat_ngram_size, no bad word "
+                             "longer than one token)")
+        B = ids.shape[0]
+        if ids.dim() != 2 or b0 < 0 or b0 + B > self.max_batch or ids.shape[1] > self.max_seq:
+            raise ValueError(f"constraint_begin: ids {tuple(ids.shape)} at row {b0} outside the "
+                             f"({self.max_batch}, {self.max_seq}) context table")
+        self.con_ctx[b0:b0 + B, :ids.shape[1]].copy_(ids.to(device=self.device, dtype=torch.int32))
+        self.pen_prev[b0:b0 + B].fill_(-1)
+
+    def constraint_forget(self, b0: int, B: int) -> None:
+        """Drop the previous token of rows [b0, b0 + B): what a prefill piece
+        before the last one sampled is no generated token, and the next piece
+        may be one token long (a decode-shaped step, which would append it)."""
+        self.pen_prev[b0:b0 + B].fill_(-1)
+
+    def constraint_snapshot(self, b0: int, B: int):
+        """A copy of the previous-token entries of rows [b0, b0 + B) (graph
+        capture runs the decode body for real: ``DecodeRing.capture`` puts them
+        back with ``constraint_restore``).  The context table itself needs no
+        copy: the capture runs write it only at positions at or beyond the
+        rows' real one, and the real replay stores each of those entries (the
+        step's previous token at ``len - 1``) before any scan reads it."""
+        return b0, B, self.pen_prev[b0:b0 + B].clone()
+
+    def constraint_restore(self, snap) -> None:
+        b0, B, prev = snap
+        self.pen_prev[b0:b0 + B].copy_(prev)
+
+    def _constrain(self, logits, b0: int, rows: int, T: int, len_pos) -> None:
+        """The constraint launch of a ``last_only`` step on its ``rows`` = B
+        logits rows; row b's context holds ``len_pos[b] + T`` tokens, the newest
+        of which a decode step (T = 1) first stores from the previous token."""
+        ctx = self.con_ctx[b0:b0 + rows] if self.con_ctx is not None else None
+        prev = self.pen_prev[b0:b0 + rows] if (T == 1 and ctx is not None) else None
+        T_.logit_constraints(logits, self.V, self.con_tables, ctx=ctx, pos=len_pos if ctx is not None else None,
+                             pos_off=T, prev=prev)
 
     # ------------------------------------------------------------------ stop conditions
     def stop_begin(self, b0: int, B: int) -> None:
@@ -723,19 +793,24 @@ class TransformerStage(StageCompute):
     def _sample_tail(self, src, ldx: int, rows: int, T: int, r0: int, b0: int, pos, out, last_only: bool, advance,
                      q8, s8, gws, lp_pos=None):
         """The last stage's work behind its blocks on ``rows`` hidden rows
-        (``src`` with row stride ``ldx``): head, penalties, suppression, argmax
-        / sampler (step operand ``pos``), log-probabilities (at ``lp_pos`` or
-        ``pos``, plus ``T - 1``), stop."""
+        (``src`` with row stride ``ldx``): head, penalties, constraints (a
+        row's context holds ``lp_pos`` or ``pos``, plus ``T``, tokens),
+        suppression, argmax / sampler (step operand ``pos``), log-probabilities
+        (at ``lp_pos`` or ``pos``, plus ``T - 1``), stop."""
         d = self.d
         lp_pos = pos if lp_pos is None else lp_pos
         logits = self.logits[r0:r0 + rows]
         pen = self.penalties_on and last_only
         lpn = self.logprobs > 0 and last_only
         stp = self.stop is not None and last_only
+        # constraints: like the penalties they change the logits behind the head, which the fused head + argmax
+        # cannot honour; `prv`: the rows' token is kept for the next decode step (penalty count, context entry)
+        con = self.constraints is not None and last_only
+        prv = pen or (con and self.con_ctx is not None)
         # min_new_tokens: the stop ids' logits are -inf while a row is below it, which the fused head + argmax
         # (its argmax comes from the unsuppressed values) cannot honour
         sup = stp and self.stop.min_new_tokens > 0 and len(self.stop.stop_token_ids) > 0
-        if self.fuse_norm and last_only and not self.temperature > 0 and not pen and not sup:
+        if self.fuse_norm and last_only and not self.temperature > 0 and not pen and not sup and not con:
             # greedy: the head writes the logits and each workgroup's argmax
             # partials; one merge launch takes the ids and the step tail
             x_last = torch.as_strided(src, (rows, d), (ldx, 1))
@@ -764,6 +839,8 @@ class TransformerStage(StageCompute):
             # penalised logits feed the unchanged argmax / sampler launches below (never the fused head, whose
             # argmax comes from the unpenalised values)
             self._penalise(logits, b0, rows, T)
+        if con:
+            self._constrain(logits, b0, rows, T, lp_pos)
         if sup:
             T_.stop_suppress(logits, self.V, self.stop_state[b0:b0 + rows], self.stop.stop_token_ids,
                              self.stop.min_new_tokens)
@@ -776,7 +853,7 @@ class TransformerStage(StageCompute):
                     T_.sample_topk(logits, nxt, self.V, self.temperature, self.top_k, self.seed, step=pos)
                 if out is not None:
                     out.copy_(nxt)
-                if pen:
+                if prv:
                     self.pen_prev[b0:b0 + rows].copy_(nxt)
                 if lpn:
                     self._record_logprobs(logits, nxt, b0, rows, T, lp_pos, False)
@@ -787,7 +864,7 @@ class TransformerStage(StageCompute):
             also, adv, hist = _advance3(advance)
             T_.sample_rows(logits, dst, self.V, self.temperature, self.top_k, self.top_p, self.min_p, self.seed,
                            step=pos, also=also, advance=adv, hist=hist)
-            if pen:
+            if prv:
                 self.pen_prev[b0:b0 + rows].copy_(dst)
             if lpn:
                 self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else lp_pos, adv is not None)
@@ -798,7 +875,7 @@ class TransformerStage(StageCompute):
         also, adv, hist = _advance3(advance)
         part = self.amx_part[r0 * 2 * T_.ARGMAX_PART_PER_ROW:] if last_only else None
         T_.argmax_rows(logits, dst, n=self.V, also=also, advance=adv, part=part, hist=hist)
-        if pen:
+        if prv:
             # the rows' token in a stage-owned place (the caller's `out` may change between calls): the next
             # decode step's penalty launch reads it from the same address on every graph replay
             self.pen_prev[b0:b0 + rows].copy_(dst)
@@ -855,7 +932,7 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                        temperature: float = 0.0, top_k: int = 0, seed: int = 0, kv_dtype: str = "bf16",
                        kv_scale: str = "calibrated", fp8_prefill: str = "e4m3", top_p: float = 1.0,
                        min_p: float = 0.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                       frequency_penalty: float = 0.0, logprobs: int = 0, stop=None):
+                       frequency_penalty: float = 0.0, logprobs: int = 0, stop=None, constraints=None):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
     info = model_info(model)
     max_seq = min(max_seq, getattr(info.cfg, "block_size", getattr(info.cfg, "max_seq", max_seq)))
@@ -863,7 +940,7 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                             temperature, top_k, seed, kv_dtype=kv_dtype, kv_scale=kv_scale, fp8_prefill=fp8_prefill,
                             top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                            logprobs=logprobs, stop=stop)
+                            logprobs=logprobs, stop=stop, constraints=constraints)
 
 
 # ---------------------------------------------------------------------- smoke / golden check

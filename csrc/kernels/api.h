@@ -202,6 +202,18 @@ int dnn_logit_constraints(void* x, int ld, int M, int N, int* ctx, int ctx_ld, c
 // B <= 0 returns 0.
 int dnn_ragged_last_rows(const void* h, int ld, const int* lens, int t0, int Tc, int B, int d, void* dst, int dst_ld,
                          hipStream_t st);
+// MXFP4 weights (gemm_w4.hip, which states the fragment order): Wq = e2m1 codes, Ws = e8m0 block scales, both
+// in fragment order (ops/w4.py pack_mxfp4).  dnn_gemm_w4: the W4A16 decode GEMM, bf16 A (lda elements per
+// row) and bf16 C; act 0..3 (3 = SiLU-mul on the packed gate|up weight, C is N / 2 wide), norm 0 / 1 RMS /
+// 2 LayerNorm folded (colsum for 2).  dnn_w4_expand: row-major bf16 W[N][ldw] of the dequantised weight.
+// Negative, nothing launched: -1 null A / Wq / Ws / C (W), or norm 2 without colsum; -2 M outside 1..64;
+// -3 K not a positive multiple of 32, N < 1, act / norm out of range, act 3 with N % 16 != 0; -4 ldc (ldr
+// with R) below the output width, lda or ldw below K; -5 A, Wq or W not 16-byte aligned, lda or ldw not a
+// multiple of 8.
+int dnn_gemm_w4(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
+                const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
+                hipStream_t st);
+int dnn_w4_expand(const void* Wq, const void* Ws, void* W, int ldw, int N, int K, hipStream_t st);
 int dnn_quant_fp8_rows(const void* x, int ldx, void* q, float* scale, int M, int K, int kpad, hipStream_t st,
                        int split = 0);
 int dnn_gemm_fp8(const void* A, const float* sa, const void* W, const float* sw, void* C, int ldc, const float* bias,

@@ -265,7 +265,7 @@ class PipelineConfig:
     num_parts: int
     return_to_node_id: Optional[str] = None
     model: str = "cifar10"
-    dtype: Optional[str] = None
+    dtype: Optional[str] = None               # transformer weights: "bf16" (default), "fp8" (e4m3), "mxfp4" (4.25-bit layer projections, bf16 head)
     kv_cache_dtype: str = "bf16"              # "fp8": OCP e4m3 KV cache (half the decode K/V bytes)
     kv_cache_scale: str = "calibrated"        # fp8 cache: per-layer scale from the first prefill's amax, or "unit"
     fp8_prefill: str = "e4m3"                 # dtype fp8: prefill activations "e4m3" (one byte, per-row scale) or "split" (e4m3 hi + residual)

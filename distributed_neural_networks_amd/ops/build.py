@@ -50,6 +50,9 @@ PER_FILE_FLAGS = {"cifar_fused.hip": ["-ffast-math"],
                   # logit_bias is one fp32 add rounded to bf16, bitwise its torch mirror
                   "constraints.hip": ["-ffp-contract=off"] + NO_SLP,
                   "gemm_skinny.hip": NO_SLP,
+                  # scalar fp32 row statistics, as gemm_skinny.hip; and no packed fp32 VALU ops
+                  # at all in this file (its GELU pairs compile to the scalar forms)
+                  "gemm_w4.hip": NO_SLP + ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                   "gemm_bf16.hip": NO_SLP}
 
 

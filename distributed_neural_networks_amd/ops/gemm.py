@@ -225,20 +225,27 @@ class FoldedLinear:
 
 
 def fold_norm(w: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor], bias: Optional[torch.Tensor],
-              rms: bool, eps: float, device, fp8: bool = False) -> FoldedLinear:
+              rms: bool, eps: float, device, fp8: bool = False, quant: Optional[str] = None) -> FoldedLinear:
     """Fold ``norm(x) @ w.T + bias`` into ``rstd * (x @ w'.T - mean * colsum) + bias'``.
 
     norm(x) = (x - mean) * rstd * gamma + beta (LayerNorm; RMSNorm: mean = 0,
     no beta), so  norm(x) @ w.T = rstd * (x @ (w * gamma).T - mean * sum_k
     (w * gamma)[n, k]) + w @ beta.  Exact in real arithmetic; colsum is taken
     from the rounded folded weight actually used by the kernel (bf16, or the
-    dequantised e4m3 weight with ``fp8=True``)."""
+    dequantised e4m3 weight with ``fp8=True``).  ``quant="mxfp4"``: the folded
+    weight becomes an ``ops.w4.Mxfp4Weight`` (colsum from its dequantised values)."""
+    if quant not in (None, "mxfp4") or (quant and fp8):
+        raise ValueError(f"fold_norm: quant {quant!r} (None or 'mxfp4', not with fp8)")
     w32 = w.to(device=device, dtype=torch.float32)
     wf32 = w32 * gamma.to(device=device, dtype=torch.float32)[None, :]
     if fp8:
         from .fp8 import quantize_weight
         wf = quantize_weight(wf32, device)
         wdq = wf.q[:, :wf32.shape[1]].float() * wf.scale[:, None]
+    elif quant == "mxfp4":
+        from .w4 import dequantize, quantize_weight_mxfp4
+        wf = quantize_weight_mxfp4(wf32, device)
+        wdq = dequantize(wf)
     else:
         wf = wf32.to(torch.bfloat16).contiguous()
         wdq = wf.float()
@@ -258,8 +265,10 @@ def linear_norm(x: torch.Tensor, f: FoldedLinear, act=None, residual: Optional[t
                 ones: Optional[torch.Tensor] = None, q8: Optional[torch.Tensor] = None,
                 s8: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
                 rs_in: Optional[torch.Tensor] = None, sx: Optional[torch.Tensor] = None,
-                q_out: Optional[tuple] = None) -> torch.Tensor:
-    """``linear(norm(x), W, b)`` for a ``FoldedLinear``.  ``rs_in`` (decode):
+                q_out: Optional[tuple] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``linear(norm(x), W, b)`` for a ``FoldedLinear``.  An MXFP4 weight
+    (``fold_norm(quant="mxfp4")``) goes to ``w4.linear_w4`` (``scratch``: its
+    bf16 expand buffer for more than 64 rows).  ``rs_in`` (decode):
     the row-statistics partials of ``x`` written by its producer (``linear(...,
     rs_out=)``), merged instead of deriving the statistics from ``x``.  Decode-sized M (<= 64):
     one skinny-GEMM launch that accumulates the row statistics from the A
@@ -270,6 +279,10 @@ def linear_norm(x: torch.Tensor, f: FoldedLinear, act=None, residual: Optional[t
     from .fp8 import Fp8Weight, linear_fp8, linear_w8
     from .fp8 import mx_ok as fp8_mx_ok
     a = _ACTS[act] if not isinstance(act, int) else act
+    from .w4 import Mxfp4Weight, linear_w4
+    if isinstance(f.w, Mxfp4Weight):
+        return linear_w4(x, f.w, f.bias, a, residual, out, f.norm, f.colsum, f.eps, scratch=scratch, std_buf=std_buf,
+                         ones=ones)
     M, K = x.shape
     w8 = isinstance(f.w, Fp8Weight)
     N = f.w.shape[0]
@@ -467,6 +480,9 @@ def attach_shuffled(w):
     passes it as ``linear(..., w_shuf=)``).  The row-major weight stays for
     prefill (M > 64), so decode weights take twice their bytes in HBM."""
     from .fp8 import Fp8Weight
+    from .w4 import Mxfp4Weight
+    if isinstance(w, Mxfp4Weight) or (isinstance(w, FoldedLinear) and isinstance(w.w, Mxfp4Weight)):
+        return w  # stored in fragment order already
     if isinstance(w, FoldedLinear):
         if isinstance(w.w, Fp8Weight):
             attach_shuffled(w.w)

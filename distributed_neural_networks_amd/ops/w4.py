@@ -1,0 +1,198 @@
+"""OCP MXFP4 weights: e2m1 codes with one e8m0 scale per 32 elements along K
+(4.25 bits per weight), the W4A16 decode GEMM and the expansion that feeds the
+bf16 prefill kernels (``csrc/kernels/gemm_w4.hip``).
+
+``Mxfp4Weight`` is the only stored copy of a weight, in the decode kernel's
+fragment order.  N is zero-padded to a multiple of 16; K must be a multiple of
+32 and is zero-padded to a multiple of 128.
+
+* ``q`` (uint8): ``[tile = n // 16][chunk = k // 128][lane = 16 g + r][16 bytes]``
+  — lane ``l`` holds the 32 codes of row ``16 tile + r``, k = ``128 chunk + 32 g
+  .. + 31`` (one MX block); byte ``b`` holds k + 2 b in its low nibble and
+  k + 2 b + 1 in its high nibble.  The 16 x 128 codes of (tile, chunk) are one
+  contiguous 1 KiB block; the blocks of a tile are consecutive along K.
+* ``scales`` (uint8 e8m0, 1..254): ``[tile][chunk][lane]``, the scale of the
+  lane's block; the value is ``2 ** (e - 127)``, as fp32 the bit pattern
+  ``e << 23``.  Pad blocks carry 127.
+
+Code ``c``: bit 3 = sign, bits 0..2 index (0, 0.5, 1, 1.5, 2, 3, 4, 6).
+
+Decode-sized M (<= 64) runs ``dnn_gemm_w4``.  More rows expand the weight into
+a caller-supplied bf16 scratch (``dnn_w4_expand``) and run the bf16 tile
+kernels on it, with their folded-norm, QKV-scatter, GELU, SwiGLU and residual
+epilogues unchanged.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from ._lib import check, lib, ptr, stream_ptr
+
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+W4_MAX_M = 64
+
+
+def _table(device) -> torch.Tensor:
+    mag = torch.tensor(E2M1, dtype=torch.float32, device=device)
+    return torch.cat([mag, -mag])
+
+
+@dataclass
+class Mxfp4Weight:
+    q: torch.Tensor       # uint8 codes in fragment order, (ceil(n / 16) * 16) * kpad / 2 bytes
+    scales: torch.Tensor  # uint8 e8m0 in fragment order, (ceil(n / 16) * 16) * kpad / 32 bytes
+    n: int
+    k: int
+
+    @property
+    def shape(self):
+        return (self.n, self.k)
+
+    @property
+    def kpad(self) -> int:
+        return -(-self.k // 128) * 128
+
+    @property
+    def npad(self) -> int:
+        return -(-self.n // 16) * 16
+
+    def _scale_rows(self) -> torch.Tensor:
+        """The scale bytes viewed as (tile, chunk, g, r): row 16 tile + r."""
+        return self.scales.view(self.npad // 16, self.kpad // 128, 4, 16)
+
+    def scale_rows_pow2(self, r: torch.Tensor) -> None:
+        """Multiply row n by ``r[n]`` (powers of two) in place: the codes stay,
+        the block exponents move."""
+        sh = torch.log2(r.float()).round().to(torch.int32)
+        if not torch.equal(torch.exp2(sh.float()), r.float()):
+            raise ValueError("scale_rows_pow2: powers of two only")
+        pad = torch.zeros(self.npad, dtype=torch.int32, device=sh.device)
+        pad[:self.n] = sh
+        e = self._scale_rows().to(torch.int32) + pad.view(-1, 1, 1, 16)
+        if int(e.min()) < 1 or int(e.max()) > 254:
+            raise ValueError("scale_rows_pow2: block exponent leaves 1..254")
+        self._scale_rows().copy_(e.to(torch.uint8))
+
+
+def pack_mxfp4(codes: torch.Tensor, exps: torch.Tensor) -> Mxfp4Weight:
+    """Raw codes (N, K) in 0..15 and e8m0 block exponents (N, K / 32) in
+    1..254 -> fragment order."""
+    N, K = codes.shape
+    if K % 32 or K == 0:
+        raise ValueError(f"pack_mxfp4: K={K} must be a positive multiple of 32 (the MX block)")
+    if tuple(exps.shape) != (N, K // 32):
+        raise ValueError(f"pack_mxfp4: exponents {tuple(exps.shape)} for codes {tuple(codes.shape)}")
+    if int(codes.min()) < 0 or int(codes.max()) > 15:
+        raise ValueError("pack_mxfp4: codes outside 0..15")
+    if int(exps.min()) < 1 or int(exps.max()) > 254:
+        raise ValueError("pack_mxfp4: e8m0 exponents outside 1..254 (0 and 255 are rejected)")
+    Np, Kp = -(-N // 16) * 16, -(-K // 128) * 128
+    c = torch.zeros((Np, Kp), dtype=torch.uint8, device=codes.device)
+    c[:N, :K] = codes.to(torch.uint8)
+    b = c[:, 0::2] | (c[:, 1::2] << 4)
+    q = b.view(Np // 16, 16, Kp // 128, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+    e = torch.full((Np, Kp // 32), 127, dtype=torch.uint8, device=codes.device)
+    e[:N, :K // 32] = exps.to(torch.uint8)
+    s = e.view(Np // 16, 16, Kp // 128, 4).permute(0, 2, 3, 1).contiguous().view(-1)
+    return Mxfp4Weight(q, s, N, K)
+
+
+def unpack_mxfp4(w: Mxfp4Weight):
+    """Inverse of ``pack_mxfp4``: codes (N, K) uint8 and exponents (N, K / 32) uint8."""
+    Np, Kp = w.npad, w.kpad
+    b = w.q.view(Np // 16, Kp // 128, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(Np, Kp // 2)
+    c = torch.stack([b & 15, b >> 4], dim=2).reshape(Np, Kp)
+    e = w._scale_rows().permute(0, 3, 1, 2).reshape(Np, Kp // 32)
+    return c[:w.n, :w.k].contiguous(), e[:w.n, :w.k // 32].contiguous()
+
+
+def dequantize(w: Mxfp4Weight) -> torch.Tensor:
+    """fp32 (N, K) values of the weight, in plain torch."""
+    c, e = unpack_mxfp4(w)
+    v = _table(c.device)[c.long()]
+    s = torch.exp2(e.float() - 127.0)
+    return (v.view(w.n, w.k // 32, 32) * s[:, :, None]).view(w.n, w.k)
+
+
+def quantize_weight_mxfp4(w: torch.Tensor, device) -> Mxfp4Weight:
+    """Round-to-nearest-even onto the e2m1 grid, saturating at +-6, with the
+    block exponent ``e = clamp(floor(log2(amax)) - 2 + 127, 1, 254)`` (127 for
+    an all-zero block): the block's amax lands in [4, 8) before rounding.
+    Idempotent on its own output."""
+    wf = w.to(device).float()
+    N, K = wf.shape
+    if K % 32 or K == 0:
+        raise ValueError(f"quantize_weight_mxfp4: K={K} must be a positive multiple of 32 (the MX block)")
+    blk = wf.view(N, K // 32, 32)
+    amax = blk.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)  # amax = m 2^ex, m in [0.5, 1): floor(log2) = ex - 1
+    e = (ex - 1 - 2 + 127).clamp(1, 254)
+    e = torch.where(amax > 0, e, torch.full_like(e, 127))
+    x = blk * torch.exp2(127.0 - e.float())[:, :, None]
+    a = x.abs().clamp(max=6.0)
+    # the grid's steps: 0.5 below 2, 1 below 4, 2 above; torch.round is half-to-even, and
+    # the even multiples of each step are the codes with an even significand
+    v = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+    idx = torch.where(v < 2, v * 2, torch.where(v < 4, v + 2, v / 2 + 4)).to(torch.uint8)
+    codes = idx | ((x < 0) & (idx > 0)).to(torch.uint8) << 3
+    return pack_mxfp4(codes.view(N, K), e.to(torch.uint8))
+
+
+def expand(w: Mxfp4Weight, scratch: torch.Tensor) -> torch.Tensor:
+    """Dequantise into the front of the bf16 ``scratch`` (``dnn_w4_expand``)
+    and return its (N, K) row-major view (row stride K)."""
+    if scratch.dtype != torch.bfloat16 or not scratch.is_contiguous() or scratch.numel() < w.n * w.k:
+        raise ValueError(f"w4.expand: contiguous bf16 scratch of >= {w.n * w.k} elements expected")
+    out = scratch.view(-1)[:w.n * w.k].view(w.n, w.k)
+    check(lib().w4_expand(ptr(w.q), ptr(w.scales), ptr(out), w.k, w.n, w.k, stream_ptr()), "w4_expand")
+    return out
+
+
+def expand_folded(f, scratch: torch.Tensor):
+    """A transient bf16 ``gemm.FoldedLinear`` over ``scratch`` holding the
+    expanded weight of the MXFP4 ``FoldedLinear`` ``f`` (same bias, colsum and
+    norm): what the bf16 prefill kernels run on.  Valid until the next
+    expansion into ``scratch``."""
+    from .gemm import FoldedLinear
+    return FoldedLinear(expand(f.w, scratch), f.bias, f.colsum, f.norm, f.eps)
+
+
+def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = None, act: int = 0,
+              residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, norm: int = 0,
+              colsum: Optional[torch.Tensor] = None, eps: float = 0.0, scratch: Optional[torch.Tensor] = None,
+              std_buf: Optional[torch.Tensor] = None, ones: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 x (M, K) times an MXFP4 weight, bf16 out.  ``norm`` (1 RMS / 2 LN,
+    with ``colsum`` for LN) is a folded pre-norm (``gemm.fold_norm(quant="mxfp4")``).
+    M <= 64: one ``dnn_gemm_w4`` launch.  M > 64: the weight is expanded into
+    ``scratch`` (bf16, >= N K elements) and the bf16 ``gemm.linear`` /
+    ``gemm.linear_norm`` run on it (``std_buf`` / ``ones`` as ``linear_norm``)."""
+    M, K = x.shape
+    N = w.n
+    if K != w.k:
+        raise ValueError(f"linear_w4: x {tuple(x.shape)} vs weight {w.shape}")
+    if x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise TypeError("linear_w4: bf16 activations with a contiguous last dim")
+    if M > W4_MAX_M:
+        from .gemm import FoldedLinear, linear, linear_norm
+        if scratch is None:
+            raise ValueError("linear_w4: more than 64 rows need the bf16 expand scratch")
+        if norm:
+            return linear_norm(x, expand_folded(FoldedLinear(w, bias, colsum, norm, eps), scratch), act, residual,
+                               out, std_buf=std_buf, ones=ones)
+        return linear(x, expand(w, scratch), bias, act, residual, out)
+    Nout = N // 2 if act == 3 else N
+    if out is None:
+        out = torch.empty((M, Nout), dtype=torch.bfloat16, device=x.device)
+    if out.dtype != torch.bfloat16 or out.stride(1) != 1 or out.shape[0] < M or out.shape[1] < Nout:
+        raise ValueError("linear_w4: bad output buffer")
+    if bias is not None and bias.dtype != torch.float32:
+        raise TypeError("linear_w4: bias must be fp32")
+    if residual is not None and (residual.shape[0] < M or residual.stride(1) != 1):
+        raise ValueError("linear_w4: bad residual")
+    check(lib().gemm_w4(ptr(x), x.stride(0), ptr(w.q), ptr(w.scales), ptr(out), out.stride(0), ptr(bias),
+                        ptr(residual), 0 if residual is None else residual.stride(0), M, N, K, act, norm,
+                        ptr(colsum), eps, stream_ptr()), "gemm_w4")
+    return out

@@ -21,6 +21,14 @@ With ``fp8=True`` every projection uses e4m3 weights (per-channel scales): in
 prefill with per-token-quantised activations on the scaled fp8 MFMA (W8A8), in
 decode as weight-only fp8 (W8A16, the weight bytes halve and the fused
 pre-norm stays) — GPT-2 XL config, and Llama-3 8B with ``dtype: fp8``.
+With ``w4=True`` (``dtype: "mxfp4"``) every layer projection is held only as an
+OCP MXFP4 weight (ops/w4.py: e2m1 codes, one e8m0 scale per 32 k, 4.25 bits per
+weight); embeddings and the vocabulary head stay bf16.  Steps of up to 64 rows
+run the W4A16 decode kernel, so a decode graph holds no other projection
+kernel; steps of more rows (prefill, chunked prefill, decode microbatches
+above 64 rows) expand each projection into the stage's one bf16 scratch and
+run the bf16 kernels on it — a decode microbatch above 64 rows therefore pays
+one expansion per projection per step.
 All positions/lengths live in device memory so a decode step is one graph.
 """
 from __future__ import annotations
@@ -85,8 +93,11 @@ class TransformerStage(StageCompute):
                  kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
                  top_p: float = 1.0, min_p: float = 0.0, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0, stop=None,
-                 constraints=None):
+                 constraints=None, w4: bool = False):
         info = model_info(model)
+        if w4 and fp8:
+            raise ValueError("w4 (MXFP4 weights) and fp8 weights exclude each other")
+        self.w4 = bool(w4)
         # fp8 weights, prefill (W8A8) activations: "e4m3" (default) = one e4m3
         # byte per activation, per-row scale, at the fp8 MFMA rate; "split" =
         # e4m3 hi + e4m3 residual planes against [W | W/16] (ops/fp8.py
@@ -164,6 +175,13 @@ class TransformerStage(StageCompute):
         self.buf_rows = max(self.max_tokens, max_batch)
         self.ones = torch.ones((self.d,), dtype=torch.float32, device=dev)
         self.layers: List[LayerW] = [self._pack_layer(sd, j) for j in range(end - start + 1)]
+        # MXFP4: the one bf16 expand scratch of the steps above 64 rows, sized to the largest projection
+        # (allocated here, never inside a graph capture)
+        self.w4_scratch = None
+        if self.w4:
+            big = max(w.n * w.k for L in self.layers
+                      for w in (L.w_qkv.w, L.w_o, L.w_up.w, L.w_down))
+            self.w4_scratch = torch.empty((big,), dtype=torch.bfloat16, device=dev)
         if first:
             if self.family == "gpt2":
                 self.wte, self.wpe = _bf(sd["wte.weight"], dev), _bf(sd["wpe.weight"], dev)
@@ -297,6 +315,7 @@ class TransformerStage(StageCompute):
         scales.  Relative to the scales already applied."""
         from ..ops.fp8 import Fp8Weight
         from ..ops.gemm import FoldedLinear, attach_shuffled
+        from ..ops.w4 import Mxfp4Weight
         qn, kn = self.H * self.hd, self.Hkv * self.hd
         for li, (L, (sk, sv)) in enumerate(zip(self.layers, scales)):
             ok, ov = self.kv_scales[li]
@@ -316,12 +335,16 @@ class TransformerStage(StageCompute):
                 L.b_qkv.mul_(r)
             if isinstance(w, Fp8Weight):
                 w.scale.mul_(r)
+            elif isinstance(w, Mxfp4Weight):
+                w.scale_rows_pow2(r)  # the block exponents move, the codes stay
             else:
                 w.mul_(r.to(w.dtype)[:, None])
                 if isinstance(L.w_qkv, FoldedLinear) and L.w_qkv.ws is not None:
                     attach_shuffled(L.w_qkv)
             if isinstance(L.w_o, Fp8Weight):
                 L.w_o.scale.mul_(rv)
+            elif isinstance(L.w_o, Mxfp4Weight):
+                L.w_o.scale_rows_pow2(torch.full((L.w_o.n,), rv, dtype=torch.float32, device=self.device))
             else:
                 L.w_o.mul_(rv)
                 if L.w_o_s is not None:
@@ -329,6 +352,9 @@ class TransformerStage(StageCompute):
             self.kv_scales[li] = (sk, sv)
 
     def _w(self, w):
+        if self.w4:
+            from ..ops.w4 import quantize_weight_mxfp4
+            return quantize_weight_mxfp4(w, self.device)
         if self.fp8:
             from ..ops.fp8 import quantize_weight
             return quantize_weight(w, self.device)
@@ -336,6 +362,7 @@ class TransformerStage(StageCompute):
 
     def _pack_layer(self, sd, j) -> LayerW:
         dev = self.device
+        quant = "mxfp4" if self.w4 else None
         if self.family == "gpt2":
             p = f"h.{j}."
             ln1_w, ln1_b = _f32(sd[p + "ln_1.weight"], dev), _f32(sd[p + "ln_1.bias"], dev)
@@ -343,8 +370,8 @@ class TransformerStage(StageCompute):
             w_qkv, b_qkv = sd[p + "attn.c_attn.weight"], sd[p + "attn.c_attn.bias"]
             w_up, b_up = sd[p + "mlp.c_fc.weight"], sd[p + "mlp.c_fc.bias"]
             if self.fuse_norm:
-                qkv_f = fold_norm(w_qkv, ln1_w, ln1_b, b_qkv, False, self.eps, dev, self.fp8)
-                up_f = fold_norm(w_up, ln2_w, ln2_b, b_up, False, self.eps, dev, self.fp8)
+                qkv_f = fold_norm(w_qkv, ln1_w, ln1_b, b_qkv, False, self.eps, dev, self.fp8, quant)
+                up_f = fold_norm(w_up, ln2_w, ln2_b, b_up, False, self.eps, dev, self.fp8, quant)
                 return LayerW(None, None, qkv_f, None,
                               self._w(sd[p + "attn.c_proj.weight"]), _f32(sd[p + "attn.c_proj.bias"], dev),
                               None, None, up_f, None,
@@ -360,9 +387,9 @@ class TransformerStage(StageCompute):
         ln1_w = _f32(sd[p + "input_layernorm.weight"], dev)
         ln2_w = _f32(sd[p + "post_attention_layernorm.weight"], dev)
         if self.fuse_norm:
-            return LayerW(None, None, fold_norm(qkv, ln1_w, None, None, True, self.eps, dev, self.fp8), None,
+            return LayerW(None, None, fold_norm(qkv, ln1_w, None, None, True, self.eps, dev, self.fp8, quant), None,
                           self._w(sd[p + "self_attn.o_proj.weight"]), None, None, None,
-                          fold_norm(gu, ln2_w, None, None, True, self.eps, dev, self.fp8), None,
+                          fold_norm(gu, ln2_w, None, None, True, self.eps, dev, self.fp8, quant), None,
                           self._w(sd[p + "mlp.down_proj.weight"]), None)
         return LayerW(ln1_w, None, self._w(qkv), None, self._w(sd[p + "self_attn.o_proj.weight"]), None,
                       ln2_w, None, self._w(gu), None, self._w(sd[p + "mlp.down_proj.weight"]), None)
@@ -614,6 +641,9 @@ class TransformerStage(StageCompute):
         ``mx_in`` (fp8 prefill): (bytes, scales) of x already MX-quantised by its
         producer.  Returns (out, whether the row statistics were written)."""
         from ..ops.gemm import rowstats_written
+        if self.w4:  # <= 64 rows: the W4A16 kernel (no producer row statistics); more: expand + bf16 GEMM
+            from ..ops.w4 import linear_w4
+            return linear_w4(x, w, b, act, residual, out, scratch=self.w4_scratch), False
         if self.fp8:
             from ..ops.fp8 import linear_fp8, linear_w8
             if skinny_rows(x.shape[0], w.q.shape[0], w8=True):  # decode: weight-only fp8 (bf16 activations)
@@ -624,6 +654,15 @@ class TransformerStage(StageCompute):
             return linear_fp8(x, w, b, act, residual, out, self.q8, self.s8, sx=self.sx8), False
         y = linear(x, w, b, act, residual, out, w_shuf=w_shuf, ws=ws, rs_out=rs_out)
         return y, rs_out is not None and rowstats_written()
+
+    def _w4x(self, f, rows: int):
+        """MXFP4 stage, more than 64 rows: the projection expanded into the
+        stage's scratch as a transient bf16 ``FoldedLinear`` (valid until the
+        next expansion: each is made right before the GEMM that reads it)."""
+        if not self.w4 or rows <= 64:
+            return f
+        from ..ops.w4 import expand_folded
+        return expand_folded(f, self.w4_scratch)
 
     # ------------------------------------------------------------------ specs
     act_dtype = torch.bfloat16  # stage-boundary hidden states
@@ -704,13 +743,14 @@ class TransformerStage(StageCompute):
         for li, L in enumerate(self.layers):
             kc, vc = self.kc[li, b0:b0 + B], self.vc[li, b0:b0 + B]
             att = self.buf_att[r0:r1]
+            w_qkv = self._w4x(L.w_qkv, ntok)
             scattered = (T > 1 and self.cos is None and self.fuse_norm and
-                         qkv_scatter_norm(h_in, L.w_qkv, a, self.buf_q, kc, vc, pos, B, T, self.H, self.Hkv,
+                         qkv_scatter_norm(h_in, w_qkv, a, self.buf_q, kc, vc, pos, B, T, self.H, self.Hkv,
                                           self.hd, ones=self.ones, q8=q8, s8=s8, sx=self.sx8 if T > 1 else None))
             if scattered:
                 pass  # prefill (no RoPE): c_attn wrote q head-major and K / V straight into the caches
             elif self.fuse_norm:
-                qkv = linear_norm(h_in, L.w_qkv, out=self.buf_qkv[r0:r1], std_buf=a, ones=self.ones, q8=q8,
+                qkv = linear_norm(h_in, w_qkv, out=self.buf_qkv[r0:r1], std_buf=a, ones=self.ones, q8=q8,
                                   s8=s8, ws=gws, rs_in=rs if have_rs else None)
             else:
                 T_.layernorm(h_in, L.ln1_w, L.ln1_b, a, self.eps, self.rms, rows=ntok)
@@ -733,7 +773,7 @@ class TransformerStage(StageCompute):
                 if (self.q8b is not None and T > 1 and up_act == ACT_GELU
                         and fp8_mx_ok(ntok, L.w_up.w.shape[0], L.w_up.w)):
                     mx_f = (self.q8b, self.sx8b)
-                f = linear_norm(h, L.w_up, act=up_act, out=self.buf_f[r0:r1], std_buf=a, ones=self.ones, q8=q8,
+                f = linear_norm(h, self._w4x(L.w_up, ntok), act=up_act, out=self.buf_f[r0:r1], std_buf=a, ones=self.ones, q8=q8,
                                 s8=s8, ws=gws, rs_in=rs if have_rs else None,
                                 sx=self.sx8 if T > 1 else None, q_out=mx_f)
                 if mx_f is not None:
@@ -934,13 +974,14 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                        min_p: float = 0.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                        frequency_penalty: float = 0.0, logprobs: int = 0, stop=None, constraints=None):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
+    w4 = dtype == "mxfp4"
     info = model_info(model)
     max_seq = min(max_seq, getattr(info.cfg, "block_size", getattr(info.cfg, "max_seq", max_seq)))
     return TransformerStage(model, sd, start, end, first, last, device, max_batch, max_seq, max_tokens, fp8,
                             temperature, top_k, seed, kv_dtype=kv_dtype, kv_scale=kv_scale, fp8_prefill=fp8_prefill,
                             top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                            logprobs=logprobs, stop=stop, constraints=constraints)
+                            logprobs=logprobs, stop=stop, constraints=constraints, w4=w4)
 
 
 # ---------------------------------------------------------------------- smoke / golden check

@@ -67,6 +67,13 @@ PYBIND11_MODULE(_dnn_hip, m) {
   }, py::arg("A"), py::arg("lda"), py::arg("Wq"), py::arg("Ws"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
      py::arg("R"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("act"), py::arg("norm"),
      py::arg("colsum"), py::arg("eps"), py::arg("st"));
+  m.def("gemm_w4_mid", [](u64 A, int lda, u64 Wq, u64 Ws, u64 C, int ldc, u64 bias, u64 R, int ldr, int M, int N,
+                          int K, int act, int norm, u64 colsum, float eps, u64 st) {
+    return dnn_gemm_w4_mid(CP(A), lda, CP(Wq), CP(Ws), P(C), ldc, CFP(bias), CP(R), ldr, M, N, K, act, norm,
+                           CFP(colsum), eps, ST(st));
+  }, py::arg("A"), py::arg("lda"), py::arg("Wq"), py::arg("Ws"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
+     py::arg("R"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("act"), py::arg("norm"),
+     py::arg("colsum"), py::arg("eps"), py::arg("st"));
   m.def("w4_expand", [](u64 Wq, u64 Ws, u64 W, int ldw, int N, int K, u64 st) {
     return dnn_w4_expand(CP(Wq), CP(Ws), P(W), ldw, N, K, ST(st));
   }, py::arg("Wq"), py::arg("Ws"), py::arg("W"), py::arg("ldw"), py::arg("N"), py::arg("K"), py::arg("st"));

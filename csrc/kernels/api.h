@@ -213,6 +213,11 @@ int dnn_ragged_last_rows(const void* h, int ld, const int* lens, int t0, int Tc,
 int dnn_gemm_w4(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
                 const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
                 hipStream_t st);
+// dnn_gemm_w4_mid (gemm_w4_mid.h): the same contract for 1 <= M <= 256 (-2 outside), one workgroup per 64 or
+// 128 columns holding all M rows, A shared through LDS; what a decode step of 65..256 rows runs.
+int dnn_gemm_w4_mid(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
+                    const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
+                    hipStream_t st);
 int dnn_w4_expand(const void* Wq, const void* Ws, void* W, int ldw, int N, int K, hipStream_t st);
 int dnn_quant_fp8_rows(const void* x, int ldx, void* q, float* scale, int M, int K, int kpad, hipStream_t st,
                        int split = 0);

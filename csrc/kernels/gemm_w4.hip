@@ -248,6 +248,12 @@ __global__ __launch_bounds__(512) void gemm_w4_kernel(const uint8_t* __restrict_
   }
 }
 
+}  // namespace dnn
+
+#include "gemm_w4_mid.h"  // dnn_gemm_w4_mid's kernel: up to 256 rows, A shared through LDS
+
+namespace dnn {
+
 constexpr int W4X_PITCH = 272;  // LDS bytes per row of a wave's 16 x 256 B block (+16: bank spread)
 
 __global__ __launch_bounds__(256) void w4_expand_kernel(const uint8_t* __restrict__ Wq, const uint8_t* __restrict__ Ws,
@@ -332,6 +338,60 @@ extern "C" int dnn_gemm_w4(const void* A, int lda, const void* Wq, const void* W
     case ACT_RELU: return launch_w4_norm<ACT_RELU>(norm, W4_ARGS);
     case ACT_GELU: return launch_w4_norm<ACT_GELU>(norm, W4_ARGS);
     default: return launch_w4_norm<ACT_SILU_MUL>(norm, W4_ARGS);
+  }
+#undef W4_ARGS
+}
+
+// dnn_gemm_w4_mid: MT = 8 (M <= 128) or 16 M tiles, NT = 2 column tiles per wave where N / 128 workgroups
+// still cover half the CUs, else 1 (gemm_w4_mid.h, "Choices").
+template <int ACT, int NORM>
+static int launch_w4_mid(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
+                         const void* R, int ldr, int M, int N, int K, const float* colsum, float eps, hipStream_t st) {
+  const int mt = (M + 15) / 16, ntile = (N + 15) / 16;
+  const size_t smem = (size_t)mt * (2 * 16 * W4M_ROW + 16 * sizeof(float2));
+#define W4M_LAUNCH(MT, NT)                                                                                        \
+  hipLaunchKernelGGL((gemm_w4_mid_kernel<ACT, NORM, MT, NT>), dim3((ntile + W4M_WAVES * NT - 1) / (W4M_WAVES * NT)), \
+                     dim3(64 * W4M_WAVES), smem, st, (const uint8_t*)A, lda * 2, (const uint8_t*)Wq,              \
+                     (const uint8_t*)Ws, (bf16_t*)C, ldc, bias, (const bf16_t*)R, ldr, M, N, K, colsum, eps)
+  if (N >= 16384) {
+    if (mt <= 8) W4M_LAUNCH(8, 2);
+    else W4M_LAUNCH(16, 2);
+  } else {
+    W4M_LAUNCH(16, 1);
+  }
+#undef W4M_LAUNCH
+  return (int)hipGetLastError();
+}
+
+template <int ACT>
+static int launch_w4_mid_norm(int norm, const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc,
+                              const float* bias, const void* R, int ldr, int M, int N, int K, const float* colsum,
+                              float eps, hipStream_t st) {
+#define W4_ARGS A, lda, Wq, Ws, C, ldc, bias, R, ldr, M, N, K, colsum, eps, st
+  switch (norm) {
+    case W4_NORM_NONE: return launch_w4_mid<ACT, W4_NORM_NONE>(W4_ARGS);
+    case W4_NORM_RMS: return launch_w4_mid<ACT, W4_NORM_RMS>(W4_ARGS);
+    default: return launch_w4_mid<ACT, W4_NORM_LN>(W4_ARGS);
+  }
+}
+
+extern "C" int dnn_gemm_w4_mid(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc,
+                               const float* bias, const void* R, int ldr, int M, int N, int K, int act, int norm,
+                               const float* colsum, float eps, hipStream_t st) {
+  if (A == nullptr || Wq == nullptr || Ws == nullptr || C == nullptr) return -1;
+  if (norm == W4_NORM_LN && colsum == nullptr) return -1;
+  if (M < 1 || M > 256) return -2;
+  if (N < 1 || K < 32 || K % 32 != 0 || act < ACT_NONE || act > ACT_SILU_MUL || norm < 0 || norm > W4_NORM_LN ||
+      (act == ACT_SILU_MUL && N % 16 != 0))
+    return -3;
+  const int NO = act == ACT_SILU_MUL ? N / 2 : N;
+  if (ldc < NO || lda < K || (R != nullptr && ldr < NO)) return -4;
+  if ((((uintptr_t)A | (uintptr_t)Wq) & 15) != 0 || (lda & 7) != 0) return -5;
+  switch (act) {
+    case ACT_NONE: return launch_w4_mid_norm<ACT_NONE>(norm, W4_ARGS);
+    case ACT_RELU: return launch_w4_mid_norm<ACT_RELU>(norm, W4_ARGS);
+    case ACT_GELU: return launch_w4_mid_norm<ACT_GELU>(norm, W4_ARGS);
+    default: return launch_w4_mid_norm<ACT_SILU_MUL>(norm, W4_ARGS);
   }
 #undef W4_ARGS
 }

@@ -268,7 +268,7 @@ def linear_norm(x: torch.Tensor, f: FoldedLinear, act=None, residual: Optional[t
                 q_out: Optional[tuple] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``linear(norm(x), W, b)`` for a ``FoldedLinear``.  An MXFP4 weight
     (``fold_norm(quant="mxfp4")``) goes to ``w4.linear_w4`` (``scratch``: its
-    bf16 expand buffer for more than 64 rows).  ``rs_in`` (decode):
+    bf16 expand buffer; without one 65..256 rows run ``dnn_gemm_w4_mid``).  ``rs_in`` (decode):
     the row-statistics partials of ``x`` written by its producer (``linear(...,
     rs_out=)``), merged instead of deriving the statistics from ``x``.  Decode-sized M (<= 64):
     one skinny-GEMM launch that accumulates the row statistics from the A

@@ -17,10 +17,13 @@ fragment order.  N is zero-padded to a multiple of 16; K must be a multiple of
 
 Code ``c``: bit 3 = sign, bits 0..2 index (0, 0.5, 1, 1.5, 2, 3, 4, 6).
 
-Decode-sized M (<= 64) runs ``dnn_gemm_w4``.  More rows expand the weight into
-a caller-supplied bf16 scratch (``dnn_w4_expand``) and run the bf16 tile
-kernels on it, with their folded-norm, QKV-scatter, GELU, SwiGLU and residual
-epilogues unchanged.
+Decode-sized M (<= 64) runs ``dnn_gemm_w4``.  65..256 rows without a scratch
+run ``dnn_gemm_w4_mid`` (``csrc/kernels/gemm_w4_mid.h``: the codes are read
+once, A is shared through LDS, nothing is expanded): the decode microbatches.
+With a caller-supplied bf16 scratch, more than 64 rows expand the weight
+(``dnn_w4_expand``) and run the bf16 tile kernels on it, with their
+folded-norm, QKV-scatter, GELU, SwiGLU and residual epilogues unchanged: the
+prefill route, and the only one above 256 rows.
 """
 from __future__ import annotations
 
@@ -33,6 +36,23 @@ from ._lib import check, lib, ptr, stream_ptr
 
 E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 W4_MAX_M = 64
+W4_MID_MAX_M = 256
+
+
+def w4_mid_ok(M: int, N: int, K: int) -> bool:
+    """Whether a decode step of 65..256 rows runs ``dnn_gemm_w4_mid`` on this
+    projection rather than expanding it (bench/probes/w4_mid_ab.py,
+    profiles/w4_mid_ab.jsonl: the mid kernel against expand + bf16 GEMM).  It
+    has no M or cross-workgroup K split, so N / 64 workgroups must fill the
+    device: N >= 4096 measured 1.2-2.2 x faster at 96..256 rows, N = 1600
+    0.66-0.97 x (slower), and N = 28672 at 256 rows a tie (excluded).  A weight
+    of at most 1 Mi elements also goes there: both routes are then bound by
+    launches, one against two (reasoned, not measured)."""
+    if not W4_MAX_M < M <= W4_MID_MAX_M:
+        return False
+    if N * K <= 1 << 20:
+        return True
+    return N >= 4096 and not (N >= 16384 and M > 128)
 
 
 def _table(device) -> torch.Tensor:
@@ -166,19 +186,21 @@ def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = No
               std_buf: Optional[torch.Tensor] = None, ones: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 x (M, K) times an MXFP4 weight, bf16 out.  ``norm`` (1 RMS / 2 LN,
     with ``colsum`` for LN) is a folded pre-norm (``gemm.fold_norm(quant="mxfp4")``).
-    M <= 64: one ``dnn_gemm_w4`` launch.  M > 64: the weight is expanded into
-    ``scratch`` (bf16, >= N K elements) and the bf16 ``gemm.linear`` /
-    ``gemm.linear_norm`` run on it (``std_buf`` / ``ones`` as ``linear_norm``)."""
+    M <= 64: one ``dnn_gemm_w4`` launch.  M > 64 with ``scratch`` (bf16, >= N K
+    elements): the weight is expanded into it and the bf16 ``gemm.linear`` /
+    ``gemm.linear_norm`` run on it (``std_buf`` / ``ones`` as ``linear_norm``).
+    65 <= M <= 256 without a scratch: one ``dnn_gemm_w4_mid`` launch on the
+    codes.  More than 256 rows need the scratch."""
     M, K = x.shape
     N = w.n
     if K != w.k:
         raise ValueError(f"linear_w4: x {tuple(x.shape)} vs weight {w.shape}")
     if x.dtype != torch.bfloat16 or x.stride(1) != 1:
         raise TypeError("linear_w4: bf16 activations with a contiguous last dim")
-    if M > W4_MAX_M:
+    if M > W4_MAX_M and (scratch is not None or M > W4_MID_MAX_M):
         from .gemm import FoldedLinear, linear, linear_norm
         if scratch is None:
-            raise ValueError("linear_w4: more than 64 rows need the bf16 expand scratch")
+            raise ValueError("linear_w4: more than 256 rows need the bf16 expand scratch")
         if norm:
             return linear_norm(x, expand_folded(FoldedLinear(w, bias, colsum, norm, eps), scratch), act, residual,
                                out, std_buf=std_buf, ones=ones)
@@ -192,7 +214,7 @@ def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = No
         raise TypeError("linear_w4: bias must be fp32")
     if residual is not None and (residual.shape[0] < M or residual.stride(1) != 1):
         raise ValueError("linear_w4: bad residual")
-    check(lib().gemm_w4(ptr(x), x.stride(0), ptr(w.q), ptr(w.scales), ptr(out), out.stride(0), ptr(bias),
-                        ptr(residual), 0 if residual is None else residual.stride(0), M, N, K, act, norm,
-                        ptr(colsum), eps, stream_ptr()), "gemm_w4")
+    fn, name = (lib().gemm_w4, "gemm_w4") if M <= W4_MAX_M else (lib().gemm_w4_mid, "gemm_w4_mid")
+    check(fn(ptr(x), x.stride(0), ptr(w.q), ptr(w.scales), ptr(out), out.stride(0), ptr(bias), ptr(residual),
+             0 if residual is None else residual.stride(0), M, N, K, act, norm, ptr(colsum), eps, stream_ptr()), name)
     return out

@@ -178,6 +178,7 @@ class TransformerStage(StageCompute):
         # MXFP4: the one bf16 expand scratch of the steps above 64 rows, sized to the largest projection
         # (allocated here, never inside a graph capture)
         self.w4_scratch = None
+        self._w4_decode = False  # the running step is a decode step (T == 1): set by ``step``
         if self.w4:
             big = max(w.n * w.k for L in self.layers
                       for w in (L.w_qkv.w, L.w_o, L.w_up.w, L.w_down))
@@ -641,9 +642,9 @@ class TransformerStage(StageCompute):
         ``mx_in`` (fp8 prefill): (bytes, scales) of x already MX-quantised by its
         producer.  Returns (out, whether the row statistics were written)."""
         from ..ops.gemm import rowstats_written
-        if self.w4:  # <= 64 rows: the W4A16 kernel (no producer row statistics); more: expand + bf16 GEMM
+        if self.w4:  # the W4A16 kernels (no producer row statistics); prefill or > 256 rows: expand + bf16 GEMM
             from ..ops.w4 import linear_w4
-            return linear_w4(x, w, b, act, residual, out, scratch=self.w4_scratch), False
+            return linear_w4(x, w, b, act, residual, out, scratch=self._w4_scratch_for(x.shape[0], w)), False
         if self.fp8:
             from ..ops.fp8 import linear_fp8, linear_w8
             if skinny_rows(x.shape[0], w.q.shape[0], w8=True):  # decode: weight-only fp8 (bf16 activations)
@@ -655,11 +656,22 @@ class TransformerStage(StageCompute):
         y = linear(x, w, b, act, residual, out, w_shuf=w_shuf, ws=ws, rs_out=rs_out)
         return y, rs_out is not None and rowstats_written()
 
+    def _w4_scratch_for(self, rows: int, w):
+        """The expand scratch where this step expands the MXFP4 weight ``w``
+        (prefill pieces of more than 64 rows, steps above 256 rows, and the
+        shapes ``w4_mid_ok`` leaves to the expansion), else None: the W4A16
+        kernels run on the codes."""
+        from ..ops.w4 import W4_MAX_M, w4_mid_ok
+        if rows <= W4_MAX_M or (self._w4_decode and w4_mid_ok(rows, w.n, w.k)):
+            return None
+        return self.w4_scratch
+
     def _w4x(self, f, rows: int):
-        """MXFP4 stage, more than 64 rows: the projection expanded into the
-        stage's scratch as a transient bf16 ``FoldedLinear`` (valid until the
-        next expansion: each is made right before the GEMM that reads it)."""
-        if not self.w4 or rows <= 64:
+        """MXFP4 stage, a step that expands (``_w4_scratch_for``): the
+        projection expanded into the stage's scratch as a transient bf16
+        ``FoldedLinear`` (valid until the next expansion: each is made right
+        before the GEMM that reads it)."""
+        if not self.w4 or self._w4_scratch_for(rows, f.w) is None:
             return f
         from ..ops.w4 import expand_folded
         return expand_folded(f, self.w4_scratch)
@@ -705,6 +717,7 @@ class TransformerStage(StageCompute):
         if advance is not None and not (self.fuses_step_tail and last_only):
             raise ValueError("step(advance=...) needs a last stage that fuses the step tail, with last_only")
         ntok = B * T
+        self._w4_decode = T == 1
         if ntok > self.buf_h.shape[0]:
             raise ValueError(f"stage buffers hold {self.buf_h.shape[0]} tokens, got {ntok}")
         if b0 + B > self.max_batch:

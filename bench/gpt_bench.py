@@ -44,7 +44,9 @@ def parse(argv=None):
                     help="one GPU group: HIP streams the microbatches of a decode round run on (0 = one, -1 = min(M, 4))")
     ap.add_argument("--prompt", type=int, default=512)
     ap.add_argument("--prefill_iters", type=int, default=5)
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"])
+    ap.add_argument("--mxfp4-prefill", dest="mxfp4_prefill", default="bf16", choices=["bf16", "e4m3"],
+                    help="mxfp4 weights: prefill pieces above 64 rows expand to bf16 (default) or run W4A8 on the codes")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="KV cache dtype (fp8: OCP e4m3)")
     ap.add_argument("--kv_scale", default="calibrated", choices=["calibrated", "unit"],
                     help="fp8 KV cache scale: per-layer, from the first prefill's amax, or unit")
@@ -72,7 +74,7 @@ def parse(argv=None):
 
 
 def _build_group(model, ranges, stage_ids, dev, max_batch, max_seq, fp8, kv="bf16", kv_scale="calibrated",
-                 fp8_prefill="e4m3"):
+                 fp8_prefill="e4m3", w4=False, mxfp4_prefill="bf16"):
     from distributed_neural_networks_amd import checkpoint as ckpt
     from distributed_neural_networks_amd.runtime.stages import TorchStage
     from distributed_neural_networks_amd.runtime.transformer import TransformerStage
@@ -87,7 +89,7 @@ def _build_group(model, ranges, stage_ids, dev, max_batch, max_seq, fp8, kv="bf1
         sd = ckpt.random_stage_state_dict(model, a, b, s == 0, s == S - 1, 0, device=dev)
         out.append(TransformerStage(model, sd, a, b, s == 0, s == S - 1, dev, max_batch=max_batch,
                                     max_seq=max_seq, fp8=fp8, kv_dtype=kv, kv_scale=kv_scale,
-                                    fp8_prefill=fp8_prefill))
+                                    fp8_prefill=fp8_prefill, w4=w4, mxfp4_prefill=mxfp4_prefill))
         del sd
     return out
 
@@ -122,7 +124,8 @@ def verify_ring(args, info, ring, grp, rep, groups, M, B, V, ranges, max_seq, fp
     if info.rank == 0:
         S = len(ranges)
         stages = _build_group(args.model, ranges, list(range(S)), dev, B * M, max_seq, fp8, kv,
-                              getattr(args, "kv_scale", "calibrated"), getattr(args, "fp8_prefill", "e4m3"))
+                              getattr(args, "kv_scale", "calibrated"), getattr(args, "fp8_prefill", "e4m3"),
+                              w4=args.dtype == "mxfp4", mxfp4_prefill=getattr(args, "mxfp4_prefill", "bf16"))
         ref = DecodeRing(stages, RingLinks(), 1, M, B, use_graphs=not args.no_graph, record=True)
         want = ref.generate([p.to(dev) for p in prompts], Tv, steps)
         del ref, stages
@@ -201,7 +204,8 @@ def run(args=None, shutdown: bool = True):
     fp8 = args.dtype == "fp8"
     kv = getattr(args, "kv", "bf16")
     stages = (_build_group(model, ranges, stage_ids, dev, B * M, max_seq, fp8, kv, getattr(args, "kv_scale", "calibrated"),
-                           getattr(args, "fp8_prefill", "e4m3"))
+                           getattr(args, "fp8_prefill", "e4m3"), w4=args.dtype == "mxfp4",
+                           mxfp4_prefill=getattr(args, "mxfp4_prefill", "bf16"))
               if stage_ids else [])
     base = rep * groups
     prev = make_link(base + grp - 1, dev) if grp > 0 else None
@@ -327,7 +331,8 @@ def run(args=None, shutdown: bool = True):
             "dtype": (("fp8-e4m3 weights (decode: W8A16 on bf16 MFMA; prefill: fp8 MFMA on split activations, "
                        "e4m3 hi + e4m3 residual), bf16 activations") if fp8 and args.fp8_prefill == "split" else
                       "fp8-e4m3 weights (decode: W8A16 on bf16 MFMA; prefill: W8A8 on fp8 MFMA), bf16 activations"
-                      if fp8 else "bf16") + ("; fp8-e4m3 KV cache" if kv == "fp8" else ""),
+                      if fp8 else f"mxfp4 weights (prefill: {getattr(args, 'mxfp4_prefill', 'bf16')}), bf16 activations"
+                      if args.dtype == "mxfp4" else "bf16") + ("; fp8-e4m3 KV cache" if kv == "fp8" else ""),
             "data": "synthetic prompts, random-init weights",
             "prefill_tokens_per_s": round(prefill_tok / prefill_s, 1),
             "prefill_ms_per_round": round(prefill_s * 1e3, 3),

@@ -74,6 +74,11 @@ PYBIND11_MODULE(_dnn_hip, m) {
   }, py::arg("A"), py::arg("lda"), py::arg("Wq"), py::arg("Ws"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
      py::arg("R"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("act"), py::arg("norm"),
      py::arg("colsum"), py::arg("eps"), py::arg("st"));
+  m.def("gemm_w4a8", [](u64 A8, u64 sx, u64 Wq, u64 Ws, u64 C, int ldc, u64 bias, u64 R, int ldr, int M, int N, int K,
+                        int act, u64 st) {
+    return dnn_gemm_w4a8(CP(A8), CP(sx), CP(Wq), CP(Ws), P(C), ldc, CFP(bias), CP(R), ldr, M, N, K, act, ST(st));
+  }, py::arg("A8"), py::arg("sx"), py::arg("Wq"), py::arg("Ws"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
+     py::arg("R"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("act"), py::arg("st"));
   m.def("w4_expand", [](u64 Wq, u64 Ws, u64 W, int ldw, int N, int K, u64 st) {
     return dnn_w4_expand(CP(Wq), CP(Ws), P(W), ldw, N, K, ST(st));
   }, py::arg("Wq"), py::arg("Ws"), py::arg("W"), py::arg("ldw"), py::arg("N"), py::arg("K"), py::arg("st"));

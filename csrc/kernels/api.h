@@ -219,6 +219,14 @@ int dnn_gemm_w4_mid(const void* A, int lda, const void* Wq, const void* Ws, void
                     const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
                     hipStream_t st);
 int dnn_w4_expand(const void* Wq, const void* Ws, void* W, int ldw, int N, int K, hipStream_t st);
+// dnn_gemm_w4a8 (gemm_w4a8.h): the MXFP4 prefill GEMM on the scaled MFMA, any M >= 1.  A8: MX e4m3 rows of
+// kpad = ceil(K / 128) * 128 bytes (pad bytes zero), sx: their e8m0 scales (mx_index, mx_mpad(M) * kpad / 128
+// bytes); Wq / Ws as dnn_gemm_w4; bf16 C / R, fp32 bias, act 0..3; no folded norm (the quantising norm pass
+// applies it).  Negative, nothing launched: -1 null A8 / sx / Wq / Ws / C; -2 M < 1; -3 K not a positive
+// multiple of 32, N < 1, act out of range, act 3 with N % 16 != 0; -4 ldc (ldr with R) below the output
+// width; -5 A8 or Wq not 16-byte aligned, sx or Ws not 4-byte aligned.
+int dnn_gemm_w4a8(const void* A8, const void* sx, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
+                  const void* R, int ldr, int M, int N, int K, int act, hipStream_t st);
 int dnn_quant_fp8_rows(const void* x, int ldx, void* q, float* scale, int M, int K, int kpad, hipStream_t st,
                        int split = 0);
 int dnn_gemm_fp8(const void* A, const float* sa, const void* W, const float* sw, void* C, int ldc, const float* bias,

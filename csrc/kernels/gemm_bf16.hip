@@ -20,13 +20,12 @@
 
 #include "api.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"  // swz_chunk, tile_coords, stage_half, bg_barrier
 
 namespace dnn {
 
 constexpr int GB_M = 128, GB_N = 128, GB_K = 64;
 constexpr int G_TILE_BYTES = GB_M * GB_K * 2;  // 16 KiB per operand tile
-
-__device__ __forceinline__ int swz_chunk(int row) { return (row >> 1) & 7; }
 
 // Stage one 128x64 bf16 tile (rows r0.., clamped to nrows-1) into LDS `dst`.
 __device__ __forceinline__ void stage_tile(const bf16_t* __restrict__ src, int ld, int r0, int nrows,
@@ -46,20 +45,6 @@ __device__ __forceinline__ void stage_tile(const bf16_t* __restrict__ src, int l
 
 __device__ __forceinline__ bf16x8 lds_frag(const char* tile, int row, int chunk) {
   return *reinterpret_cast<const bf16x8*>(tile + row * 128 + ((chunk ^ swz_chunk(row)) << 4));
-}
-
-// Tile order: the XCD remap gives each XCD a contiguous run of logical ids;
-// inside it tiles go GROUP_M rows of M-tiles at a time, M fastest, so the ~32-64
-// tiles co-resident on one XCD share a few A and W panels in its L2.
-__device__ __forceinline__ void tile_coords(int logical, int ntm, int ntn, int& tm, int& tn) {
-  constexpr int GROUP_M = 8;
-  const int per_group = GROUP_M * ntn;
-  const int grp = logical / per_group;
-  const int first = grp * GROUP_M;
-  const int gm = min(ntm - first, GROUP_M);
-  const int r = logical - grp * per_group;
-  tm = first + r % gm;
-  tn = r / gm;
 }
 
 // Epilogue on a TRANSPOSED accumulator: the MFMAs are issued as W.A^T, so a
@@ -192,20 +177,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_kernel(
 constexpr int BG_M = 256, BG_N = 256, BG_K = 64;
 constexpr int BG_HALF = 128 * BG_K * 2;  // 16 KiB
 
-// Stage one 128x64 half-tile: 2 glds per thread, 8 rows per wave-instruction.
-__device__ __forceinline__ void stage_half(const bf16_t* __restrict__ src, int ld, int r0, int nrows, int k0,
-                                           char* dst, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int piece = i * 8 + wave;
-    const int rl = piece * 8 + (lane >> 3);
-    const int cs = (lane & 7) ^ swz_chunk(rl);
-    int r = r0 + rl;
-    r = r < nrows ? r : nrows - 1;
-    glds16(src + (size_t)r * ld + k0 + cs * 8, dst + piece * 1024);
-  }
-}
-
+// (stage_half, one 128x64 half-tile by 2 glds per thread: gemm_tile.h)
 // Epilogue operands of a 256^2 tile by LDS-DMA, into EPI_LDS bytes past the
 // operand buffers, issued before the first staging DMA (so the prologue's
 // counted wait retires them and no register carries them through the main
@@ -239,12 +211,6 @@ __device__ __forceinline__ void epi_operands_dma(const float* bias, const float*
   if ((wave == 2 || wave == 3) && rowstat != nullptr)
     glds16(rowstat + min(m0 + (wave - 2) * 128 + 2 * lane, M - 2), dst + EPI_RS + (wave - 2) * 1024);
   if (wave == 4 && sa != nullptr) glds16(sa + min(m0 + 4 * lane, M - 4), dst + EPI_SA);
-}
-
-__device__ __forceinline__ void bg_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
 }
 
 template <int MI, int NJ>

@@ -251,6 +251,7 @@ __global__ __launch_bounds__(512) void gemm_w4_kernel(const uint8_t* __restrict_
 }  // namespace dnn
 
 #include "gemm_w4_mid.h"  // dnn_gemm_w4_mid's kernel: up to 256 rows, A shared through LDS
+#include "gemm_w4a8.h"    // dnn_gemm_w4a8: prefill on MX e4m3 activations, the codes on the scaled MFMA
 
 namespace dnn {
 

@@ -269,7 +269,8 @@ def build_stage(ctx: NodeContext, part: int, ranges, device: torch.device, full_
                                     repetition_penalty=pipe.repetition_penalty,
                                     presence_penalty=pipe.presence_penalty,
                                     frequency_penalty=pipe.frequency_penalty, logprobs=pipe.logprobs,
-                                    stop=pipe.stop, constraints=pipe.constraints)
+                                    stop=pipe.stop, constraints=pipe.constraints,
+                                    mxfp4_prefill=pipe.mxfp4_prefill)
     else:
         st = TorchStage(pipe.model, sd, a, b, first, last, device,
                         sampling=(pipe.temperature, pipe.top_k, pipe.seed, pipe.top_p, pipe.min_p,

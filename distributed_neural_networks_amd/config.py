@@ -16,7 +16,7 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
   ``logprobs``, ``eos_token_id``, ``stop_token_ids``, ``stop_sequences``, ``min_new_tokens``,
   ``pad_token_id``, ``logit_bias``, ``allowed_token_ids``, ``bad_words_ids``, ``no_repeat_ngram_size``,
   ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
-  ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``input_dtype``, ``input_mean``,
+  ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``mxfp4_prefill``, ``input_dtype``, ``input_mean``,
   ``input_std`` (CIFAR: stage 0 takes uint8 images and normalises them by table); per node
   ``layers: [start, end]`` (inclusive, as in
   ``partitions/gpt_model_parts.py:12``) and ``device``.
@@ -269,6 +269,7 @@ class PipelineConfig:
     kv_cache_dtype: str = "bf16"              # "fp8": OCP e4m3 KV cache (half the decode K/V bytes)
     kv_cache_scale: str = "calibrated"        # fp8 cache: per-layer scale from the first prefill's amax, or "unit"
     fp8_prefill: str = "e4m3"                 # dtype fp8: prefill activations "e4m3" (one byte, per-row scale) or "split" (e4m3 hi + residual)
+    mxfp4_prefill: str = "bf16"               # dtype mxfp4: prefill above 64 rows "bf16" (expand + bf16 GEMM) or "e4m3" (W4A8 on the codes)
     transport: str = "grpc"
     micro_batch_size: int = 1
     num_microbatches: int = 1
@@ -422,6 +423,11 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
     fpp = cfg.get("fp8_prefill", "e4m3")
     if fpp not in ("split", "e4m3"):
         raise ConfigError(f"ERROR: 'fp8_prefill' must be 'split' or 'e4m3', got {fpp!r}")
+    m4p = cfg.get("mxfp4_prefill", "bf16")
+    if m4p not in ("bf16", "e4m3"):
+        raise ConfigError(f"ERROR: 'mxfp4_prefill' must be 'bf16' or 'e4m3', got {m4p!r}")
+    if m4p != "bf16" and cfg.get("dtype") != "mxfp4":
+        raise ConfigError(f"ERROR: 'mxfp4_prefill' {m4p!r} needs dtype 'mxfp4', got {cfg.get('dtype')!r}")
     kvs = cfg.get("kv_cache_scale", "calibrated")
     if kvs not in ("calibrated", "unit"):
         raise ConfigError(f"ERROR: 'kv_cache_scale' must be 'calibrated' or 'unit', got {kvs!r}")
@@ -499,7 +505,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
     return PipelineConfig(
         nodes=nodes, model_weights=str(weights), num_parts=num_parts,
         return_to_node_id=cfg.get("return_to_node_id"), model=model, dtype=cfg.get("dtype"), kv_cache_dtype=kvd,
-        kv_cache_scale=kvs, fp8_prefill=fpp,
+        kv_cache_scale=kvs, fp8_prefill=fpp, mxfp4_prefill=m4p,
         transport=transport, micro_batch_size=int(cfg.get("micro_batch_size", 1)),
         num_microbatches=int(cfg.get("num_microbatches", 1)), seq_len=int(cfg.get("seq_len", 64)),
         prompt_len=cfg.get("prompt_len"), prompts=prompts, decode_steps=int(cfg.get("decode_steps", 0)),

@@ -268,7 +268,8 @@ def linear_norm(x: torch.Tensor, f: FoldedLinear, act=None, residual: Optional[t
                 q_out: Optional[tuple] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``linear(norm(x), W, b)`` for a ``FoldedLinear``.  An MXFP4 weight
     (``fold_norm(quant="mxfp4")``) goes to ``w4.linear_w4`` (``scratch``: its
-    bf16 expand buffer; without one 65..256 rows run ``dnn_gemm_w4_mid``).  ``rs_in`` (decode):
+    bf16 expand buffer; without one 65..256 rows run ``dnn_gemm_w4_mid``), or, with ``q8`` and
+    ``sx`` given, to ``layernorm_q8_mx`` + ``w4.linear_w4a8`` (MX e4m3 activations).  ``rs_in`` (decode):
     the row-statistics partials of ``x`` written by its producer (``linear(...,
     rs_out=)``), merged instead of deriving the statistics from ``x``.  Decode-sized M (<= 64):
     one skinny-GEMM launch that accumulates the row statistics from the A
@@ -279,8 +280,17 @@ def linear_norm(x: torch.Tensor, f: FoldedLinear, act=None, residual: Optional[t
     from .fp8 import Fp8Weight, linear_fp8, linear_w8
     from .fp8 import mx_ok as fp8_mx_ok
     a = _ACTS[act] if not isinstance(act, int) else act
-    from .w4 import Mxfp4Weight, linear_w4
+    from .w4 import Mxfp4Weight, linear_w4, linear_w4a8
     if isinstance(f.w, Mxfp4Weight):
+        if q8 is not None and sx is not None:
+            # W4A8 prefill: standardise + MX-quantise in one pass (gain ``ones``), then the codes on the
+            # scaled MFMA; the folded weight and bias do the rest (no colsum on this route)
+            from .transformer_ops import layernorm_q8_mx
+            if ones is None:
+                raise ValueError("linear_norm: the W4A8 route needs ones")
+            M = x.shape[0]
+            layernorm_q8_mx(x, ones, None, q8, sx, f.w.kpad, f.eps, f.norm == NORM_RMS, rows=M, ldx=x.stride(0))
+            return linear_w4a8(x, f.w, f.bias, a, residual, out, q8, sx, prequantized=True)
         return linear_w4(x, f.w, f.bias, a, residual, out, f.norm, f.colsum, f.eps, scratch=scratch, std_buf=std_buf,
                          ones=ones)
     M, K = x.shape

@@ -180,6 +180,44 @@ def expand_folded(f, scratch: torch.Tensor):
     return FoldedLinear(expand(f.w, scratch), f.bias, f.colsum, f.norm, f.eps)
 
 
+def linear_w4a8(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = None, act: int = 0,
+                residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                q8: Optional[torch.Tensor] = None, sx: Optional[torch.Tensor] = None,
+                prequantized: bool = False) -> torch.Tensor:
+    """bf16 x (M, K) times an MXFP4 weight on MX e4m3 activations (W4A8,
+    ``dnn_gemm_w4a8``: the codes on the scaled MFMA, nothing expanded), bf16
+    out, any M >= 1: the prefill route of ``mxfp4_prefill: "e4m3"``.  ``q8``
+    (>= M * kpad bytes) and ``sx`` (>= ``fp8.mx_scale_bytes(M, kpad)`` bytes)
+    receive the quantised rows and their e8m0 scales (``fp8.quant_rows_mx``);
+    with ``prequantized`` they already hold them (``layernorm_q8_mx``) and x
+    only gives M and K."""
+    from .fp8 import mx_scale_bytes, quant_rows_mx
+    M, K = x.shape
+    N, kp = w.n, w.kpad
+    if K != w.k:
+        raise ValueError(f"linear_w4a8: x {tuple(x.shape)} vs weight {w.shape}")
+    if x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise TypeError("linear_w4a8: bf16 activations with a contiguous last dim")
+    if q8 is None or sx is None or q8.numel() * q8.element_size() < M * kp or \
+            sx.numel() * sx.element_size() < mx_scale_bytes(M, kp):
+        raise ValueError(f"linear_w4a8: q8 of >= {M * kp} bytes and sx of >= {mx_scale_bytes(M, kp)} bytes expected")
+    Nout = N // 2 if act == 3 else N
+    if out is None:
+        out = torch.empty((M, Nout), dtype=torch.bfloat16, device=x.device)
+    if out.dtype != torch.bfloat16 or out.stride(1) != 1 or out.shape[0] < M or out.shape[1] < Nout:
+        raise ValueError("linear_w4a8: bad output buffer")
+    if bias is not None and bias.dtype != torch.float32:
+        raise TypeError("linear_w4a8: bias must be fp32")
+    if residual is not None and (residual.shape[0] < M or residual.stride(1) != 1):
+        raise ValueError("linear_w4a8: bad residual")
+    if not prequantized:
+        quant_rows_mx(x, q8, sx, M)
+    check(lib().gemm_w4a8(ptr(q8), ptr(sx), ptr(w.q), ptr(w.scales), ptr(out), out.stride(0), ptr(bias),
+                          ptr(residual), 0 if residual is None else residual.stride(0), M, N, K, act, stream_ptr()),
+          "gemm_w4a8")
+    return out
+
+
 def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = None, act: int = 0,
               residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, norm: int = 0,
               colsum: Optional[torch.Tensor] = None, eps: float = 0.0, scratch: Optional[torch.Tensor] = None,

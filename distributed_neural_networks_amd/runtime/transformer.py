@@ -93,11 +93,19 @@ class TransformerStage(StageCompute):
                  kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
                  top_p: float = 1.0, min_p: float = 0.0, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0, stop=None,
-                 constraints=None, w4: bool = False):
+                 constraints=None, w4: bool = False, mxfp4_prefill: str = "bf16"):
         info = model_info(model)
         if w4 and fp8:
             raise ValueError("w4 (MXFP4 weights) and fp8 weights exclude each other")
         self.w4 = bool(w4)
+        # MXFP4 weights, prefill pieces of more than 64 rows: "bf16" (default) = expand each projection to
+        # bf16 and run the bf16 tile kernels; "e4m3" = MX e4m3 activations against the codes on the scaled
+        # MFMA (ops/w4.py linear_w4a8: no expansion, the fp8 MFMA rate)
+        if mxfp4_prefill not in ("bf16", "e4m3"):
+            raise ValueError(f"mxfp4_prefill {mxfp4_prefill!r}: bf16 or e4m3")
+        if mxfp4_prefill != "bf16" and not w4:
+            raise ValueError("mxfp4_prefill 'e4m3' needs MXFP4 weights (dtype mxfp4)")
+        self.mxfp4_prefill = mxfp4_prefill
         # fp8 weights, prefill (W8A8) activations: "e4m3" (default) = one e4m3
         # byte per activation, per-row scale, at the fp8 MFMA rate; "split" =
         # e4m3 hi + e4m3 residual planes against [W | W/16] (ops/fp8.py
@@ -179,6 +187,7 @@ class TransformerStage(StageCompute):
         # (allocated here, never inside a graph capture)
         self.w4_scratch = None
         self._w4_decode = False  # the running step is a decode step (T == 1): set by ``step``
+        self._w4_a8 = False      # the running step is a W4A8 prefill piece (mxfp4_prefill "e4m3"): set by ``step``
         if self.w4:
             big = max(w.n * w.k for L in self.layers
                       for w in (L.w_qkv.w, L.w_o, L.w_up.w, L.w_down))
@@ -432,6 +441,12 @@ class TransformerStage(StageCompute):
                 self.sx8 = torch.empty((mx_scale_bytes(ntok, kmax),), dtype=torch.uint8, device=dev)
                 self.q8b = torch.empty((ntok * kpad_of(ffn),), dtype=torch.uint8, device=dev)
                 self.sx8b = torch.empty((mx_scale_bytes(ntok, kpad_of(ffn)),), dtype=torch.uint8, device=dev)
+        if self.w4 and self.mxfp4_prefill == "e4m3":
+            # W4A8 prefill: the MX e4m3 rows and e8m0 scales of a projection's input, sized as the fp8 stage's
+            from ..ops.fp8 import kpad_of, mx_scale_bytes
+            kmax = max(kpad_of(d), kpad_of(ffn))
+            self.q8 = torch.empty((ntok * kmax,), dtype=torch.uint8, device=dev)
+            self.sx8 = torch.empty((mx_scale_bytes(ntok, kmax),), dtype=torch.uint8, device=dev)
         if self.last:
             # ragged prompts: each row's hidden state at its own last prompt position, and the sampler's
             # step operand of their first token; allocated by the first step(lens=...) (_ragged_buffers)
@@ -643,7 +658,9 @@ class TransformerStage(StageCompute):
         producer.  Returns (out, whether the row statistics were written)."""
         from ..ops.gemm import rowstats_written
         if self.w4:  # the W4A16 kernels (no producer row statistics); prefill or > 256 rows: expand + bf16 GEMM
-            from ..ops.w4 import linear_w4
+            from ..ops.w4 import linear_w4, linear_w4a8
+            if self._w4_a8:  # W4A8 prefill piece: quantise pass + the codes on the scaled MFMA
+                return linear_w4a8(x, w, b, act, residual, out, self.q8, self.sx8), False
             return linear_w4(x, w, b, act, residual, out, scratch=self._w4_scratch_for(x.shape[0], w)), False
         if self.fp8:
             from ..ops.fp8 import linear_fp8, linear_w8
@@ -662,7 +679,7 @@ class TransformerStage(StageCompute):
         shapes ``w4_mid_ok`` leaves to the expansion), else None: the W4A16
         kernels run on the codes."""
         from ..ops.w4 import W4_MAX_M, w4_mid_ok
-        if rows <= W4_MAX_M or (self._w4_decode and w4_mid_ok(rows, w.n, w.k)):
+        if rows <= W4_MAX_M or self._w4_a8 or (self._w4_decode and w4_mid_ok(rows, w.n, w.k)):
             return None
         return self.w4_scratch
 
@@ -718,6 +735,8 @@ class TransformerStage(StageCompute):
             raise ValueError("step(advance=...) needs a last stage that fuses the step tail, with last_only")
         ntok = B * T
         self._w4_decode = T == 1
+        # W4A8 (mxfp4_prefill "e4m3"): every prefill piece of more than 64 rows, whatever its shape
+        a8 = self._w4_a8 = self.w4 and self.mxfp4_prefill == "e4m3" and T > 1 and ntok > 64
         if ntok > self.buf_h.shape[0]:
             raise ValueError(f"stage buffers hold {self.buf_h.shape[0]} tokens, got {ntok}")
         if b0 + B > self.max_batch:
@@ -741,6 +760,8 @@ class TransformerStage(StageCompute):
         h = self.buf_h[r0:r1]
         a = self.buf_a[r0:r1]
         q8, s8 = self.q8, self.s8
+        if self.w4 and not a8:
+            q8 = None  # the W4A16 routes quantise nothing
         if self.fp8 and T == 1:
             q8 = self.q8[r0 * (self.q8.numel() // self.buf_rows):]
             s8 = self.s8[r0:]
@@ -757,14 +778,14 @@ class TransformerStage(StageCompute):
             kc, vc = self.kc[li, b0:b0 + B], self.vc[li, b0:b0 + B]
             att = self.buf_att[r0:r1]
             w_qkv = self._w4x(L.w_qkv, ntok)
-            scattered = (T > 1 and self.cos is None and self.fuse_norm and
+            scattered = (not a8 and T > 1 and self.cos is None and self.fuse_norm and
                          qkv_scatter_norm(h_in, w_qkv, a, self.buf_q, kc, vc, pos, B, T, self.H, self.Hkv,
                                           self.hd, ones=self.ones, q8=q8, s8=s8, sx=self.sx8 if T > 1 else None))
             if scattered:
                 pass  # prefill (no RoPE): c_attn wrote q head-major and K / V straight into the caches
             elif self.fuse_norm:
                 qkv = linear_norm(h_in, w_qkv, out=self.buf_qkv[r0:r1], std_buf=a, ones=self.ones, q8=q8,
-                                  s8=s8, ws=gws, rs_in=rs if have_rs else None)
+                                  s8=s8, ws=gws, rs_in=rs if have_rs else None, sx=self.sx8 if a8 else None)
             else:
                 T_.layernorm(h_in, L.ln1_w, L.ln1_b, a, self.eps, self.rms, rows=ntok)
                 qkv, _ = self._lin(a, L.w_qkv, L.b_qkv, out=self.buf_qkv[r0:r1])
@@ -985,7 +1006,8 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                        temperature: float = 0.0, top_k: int = 0, seed: int = 0, kv_dtype: str = "bf16",
                        kv_scale: str = "calibrated", fp8_prefill: str = "e4m3", top_p: float = 1.0,
                        min_p: float = 0.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                       frequency_penalty: float = 0.0, logprobs: int = 0, stop=None, constraints=None):
+                       frequency_penalty: float = 0.0, logprobs: int = 0, stop=None, constraints=None,
+                       mxfp4_prefill: str = "bf16"):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
     w4 = dtype == "mxfp4"
     info = model_info(model)
@@ -994,7 +1016,8 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                             temperature, top_k, seed, kv_dtype=kv_dtype, kv_scale=kv_scale, fp8_prefill=fp8_prefill,
                             top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                            logprobs=logprobs, stop=stop, constraints=constraints, w4=w4)
+                            logprobs=logprobs, stop=stop, constraints=constraints, w4=w4,
+                            mxfp4_prefill=mxfp4_prefill)
 
 
 # ---------------------------------------------------------------------- smoke / golden check

@@ -47,6 +47,8 @@ def parse(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"])
     ap.add_argument("--mxfp4-prefill", dest="mxfp4_prefill", default="bf16", choices=["bf16", "e4m3"],
                     help="mxfp4 weights: prefill pieces above 64 rows expand to bf16 (default) or run W4A8 on the codes")
+    ap.add_argument("--mxfp4-head", dest="mxfp4_head", action="store_true",
+                    help="mxfp4 weights: the vocabulary head as a folded MXFP4 weight too (mxfp4_head: \"mxfp4\")")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="KV cache dtype (fp8: OCP e4m3)")
     ap.add_argument("--kv_scale", default="calibrated", choices=["calibrated", "unit"],
                     help="fp8 KV cache scale: per-layer, from the first prefill's amax, or unit")
@@ -74,7 +76,7 @@ def parse(argv=None):
 
 
 def _build_group(model, ranges, stage_ids, dev, max_batch, max_seq, fp8, kv="bf16", kv_scale="calibrated",
-                 fp8_prefill="e4m3", w4=False, mxfp4_prefill="bf16"):
+                 fp8_prefill="e4m3", w4=False, mxfp4_prefill="bf16", mxfp4_head="bf16"):
     from distributed_neural_networks_amd import checkpoint as ckpt
     from distributed_neural_networks_amd.runtime.stages import TorchStage
     from distributed_neural_networks_amd.runtime.transformer import TransformerStage
@@ -89,7 +91,8 @@ def _build_group(model, ranges, stage_ids, dev, max_batch, max_seq, fp8, kv="bf1
         sd = ckpt.random_stage_state_dict(model, a, b, s == 0, s == S - 1, 0, device=dev)
         out.append(TransformerStage(model, sd, a, b, s == 0, s == S - 1, dev, max_batch=max_batch,
                                     max_seq=max_seq, fp8=fp8, kv_dtype=kv, kv_scale=kv_scale,
-                                    fp8_prefill=fp8_prefill, w4=w4, mxfp4_prefill=mxfp4_prefill))
+                                    fp8_prefill=fp8_prefill, w4=w4, mxfp4_prefill=mxfp4_prefill,
+                                    mxfp4_head=mxfp4_head))
         del sd
     return out
 
@@ -125,7 +128,8 @@ def verify_ring(args, info, ring, grp, rep, groups, M, B, V, ranges, max_seq, fp
         S = len(ranges)
         stages = _build_group(args.model, ranges, list(range(S)), dev, B * M, max_seq, fp8, kv,
                               getattr(args, "kv_scale", "calibrated"), getattr(args, "fp8_prefill", "e4m3"),
-                              w4=args.dtype == "mxfp4", mxfp4_prefill=getattr(args, "mxfp4_prefill", "bf16"))
+                              w4=args.dtype == "mxfp4", mxfp4_prefill=getattr(args, "mxfp4_prefill", "bf16"),
+                              mxfp4_head="mxfp4" if getattr(args, "mxfp4_head", False) else "bf16")
         ref = DecodeRing(stages, RingLinks(), 1, M, B, use_graphs=not args.no_graph, record=True)
         want = ref.generate([p.to(dev) for p in prompts], Tv, steps)
         del ref, stages
@@ -205,7 +209,8 @@ def run(args=None, shutdown: bool = True):
     kv = getattr(args, "kv", "bf16")
     stages = (_build_group(model, ranges, stage_ids, dev, B * M, max_seq, fp8, kv, getattr(args, "kv_scale", "calibrated"),
                            getattr(args, "fp8_prefill", "e4m3"), w4=args.dtype == "mxfp4",
-                           mxfp4_prefill=getattr(args, "mxfp4_prefill", "bf16"))
+                           mxfp4_prefill=getattr(args, "mxfp4_prefill", "bf16"),
+                           mxfp4_head="mxfp4" if getattr(args, "mxfp4_head", False) else "bf16")
               if stage_ids else [])
     base = rep * groups
     prev = make_link(base + grp - 1, dev) if grp > 0 else None
@@ -331,7 +336,8 @@ def run(args=None, shutdown: bool = True):
             "dtype": (("fp8-e4m3 weights (decode: W8A16 on bf16 MFMA; prefill: fp8 MFMA on split activations, "
                        "e4m3 hi + e4m3 residual), bf16 activations") if fp8 and args.fp8_prefill == "split" else
                       "fp8-e4m3 weights (decode: W8A16 on bf16 MFMA; prefill: W8A8 on fp8 MFMA), bf16 activations"
-                      if fp8 else f"mxfp4 weights (prefill: {getattr(args, 'mxfp4_prefill', 'bf16')}), bf16 activations"
+                      if fp8 else f"mxfp4 weights (prefill: {getattr(args, 'mxfp4_prefill', 'bf16')}, head: "
+                      f"{'mxfp4' if getattr(args, 'mxfp4_head', False) else 'bf16'}), bf16 activations"
                       if args.dtype == "mxfp4" else "bf16") + ("; fp8-e4m3 KV cache" if kv == "fp8" else ""),
             "data": "synthetic prompts, random-init weights",
             "prefill_tokens_per_s": round(prefill_tok / prefill_s, 1),

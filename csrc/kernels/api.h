@@ -219,6 +219,17 @@ int dnn_gemm_w4_mid(const void* A, int lda, const void* Wq, const void* Ws, void
                     const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
                     hipStream_t st);
 int dnn_w4_expand(const void* Wq, const void* Ws, void* W, int ldw, int N, int K, hipStream_t st);
+// dnn_gemm_w4_head (gemm_w4_head.h): the MXFP4 vocabulary head, 1 <= M <= 64: bf16 logits C = norm-folded
+// A . dq(W)^T + bias from persistent workgroups (at most one per CU, A in LDS), and with part != nullptr each
+// workgroup's argmax per row of the rounded logits as int2 {value bits, index} at part[row * S + wg]
+// (dnn_gemm_head's format, merged by dnn_argmax_final; ties -> smallest index).  Returns S, the partials per
+// row (> 0; the workgroups), also with part == nullptr (logits only).  Negative, nothing launched: -1 null A /
+// Wq / Ws / C, or norm 2 without colsum; -2 M outside 1..64; -3 K not a positive multiple of 32, N < 1, norm
+// out of range, part_cap (int2 per row in part) below S; -4 ldc below N, lda below K; -5 A, Wq or C not
+// 16-byte aligned, lda or ldc not a multiple of 8; -6 / -7: the device query or the launch failed.
+int dnn_gemm_w4_head(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
+                     int M, int N, int K, int norm, const float* colsum, float eps, void* part, int part_cap,
+                     hipStream_t st);
 // dnn_gemm_w4a8 (gemm_w4a8.h): the MXFP4 prefill GEMM on the scaled MFMA, any M >= 1.  A8: MX e4m3 rows of
 // kpad = ceil(K / 128) * 128 bytes (pad bytes zero), sx: their e8m0 scales (mx_index, mx_mpad(M) * kpad / 128
 // bytes); Wq / Ws as dnn_gemm_w4; bf16 C / R, fp32 bias, act 0..3; no folded norm (the quantising norm pass

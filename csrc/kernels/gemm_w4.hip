@@ -252,6 +252,7 @@ __global__ __launch_bounds__(512) void gemm_w4_kernel(const uint8_t* __restrict_
 
 #include "gemm_w4_mid.h"  // dnn_gemm_w4_mid's kernel: up to 256 rows, A shared through LDS
 #include "gemm_w4a8.h"    // dnn_gemm_w4a8: prefill on MX e4m3 activations, the codes on the scaled MFMA
+#include "gemm_w4_head.h"  // dnn_gemm_w4_head: the vocabulary head, persistent workgroups, argmax partials
 
 namespace dnn {
 
@@ -395,6 +396,47 @@ extern "C" int dnn_gemm_w4_mid(const void* A, int lda, const void* Wq, const voi
     default: return launch_w4_mid_norm<ACT_SILU_MUL>(norm, W4_ARGS);
   }
 #undef W4_ARGS
+}
+
+// dnn_gemm_w4_head: one persistent workgroup per 8 column tiles, at most one per CU (gemm_w4_head.h).
+static int w4_head_cus() {
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (cus[dev] == 0) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    cus[dev] = v;
+  }
+  return cus[dev];
+}
+
+extern "C" int dnn_gemm_w4_head(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc,
+                                const float* bias, int M, int N, int K, int norm, const float* colsum, float eps,
+                                void* part, int part_cap, hipStream_t st) {
+  if (A == nullptr || Wq == nullptr || Ws == nullptr || C == nullptr) return -1;
+  if (norm == W4_NORM_LN && colsum == nullptr) return -1;
+  if (M < 1 || M > 64) return -2;
+  if (N < 1 || K < 32 || K % 32 != 0 || norm < 0 || norm > W4_NORM_LN) return -3;
+  const int ntile = (N + 15) / 16, cus = w4_head_cus();
+  if (cus <= 0) return -6;
+  const int grid = std::min(cus, (ntile + W4H_WAVES - 1) / W4H_WAVES);
+  if (part != nullptr && part_cap < grid) return -3;
+  if (ldc < N || lda < K) return -4;
+  if ((((uintptr_t)A | (uintptr_t)Wq | (uintptr_t)C) & 15) != 0 || (lda & 7) != 0 || (ldc & 7) != 0) return -5;
+  const int mt = (M + 15) / 16, nch = (K + 127) / 128, cpp = std::min(nch, W4H_IMG / mt);
+  const size_t smem = (size_t)mt * 16 * cpp * 256 + W4H_TAIL;
+#define W4H_LAUNCH(NORM)                                                                                          \
+  hipLaunchKernelGGL((gemm_w4_head_kernel<NORM>), dim3(grid), dim3(64 * W4H_WAVES), smem, st, (const uint8_t*)A, \
+                     lda * 2, (const uint8_t*)Wq, (const uint8_t*)Ws, (bf16_t*)C, ldc, bias, colsum, eps, M, N, K, \
+                     (int2*)part)
+  switch (norm) {
+    case W4_NORM_NONE: W4H_LAUNCH(W4_NORM_NONE); break;
+    case W4_NORM_RMS: W4H_LAUNCH(W4_NORM_RMS); break;
+    default: W4H_LAUNCH(W4_NORM_LN); break;
+  }
+#undef W4H_LAUNCH
+  return hipGetLastError() != hipSuccess ? -7 : grid;
 }
 
 extern "C" int dnn_w4_expand(const void* Wq, const void* Ws, void* W, int ldw, int N, int K, hipStream_t st) {

@@ -270,7 +270,7 @@ def build_stage(ctx: NodeContext, part: int, ranges, device: torch.device, full_
                                     presence_penalty=pipe.presence_penalty,
                                     frequency_penalty=pipe.frequency_penalty, logprobs=pipe.logprobs,
                                     stop=pipe.stop, constraints=pipe.constraints,
-                                    mxfp4_prefill=pipe.mxfp4_prefill)
+                                    mxfp4_prefill=pipe.mxfp4_prefill, mxfp4_head=pipe.mxfp4_head)
     else:
         st = TorchStage(pipe.model, sd, a, b, first, last, device,
                         sampling=(pipe.temperature, pipe.top_k, pipe.seed, pipe.top_p, pipe.min_p,

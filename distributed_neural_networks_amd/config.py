@@ -16,7 +16,7 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
   ``logprobs``, ``eos_token_id``, ``stop_token_ids``, ``stop_sequences``, ``min_new_tokens``,
   ``pad_token_id``, ``logit_bias``, ``allowed_token_ids``, ``bad_words_ids``, ``no_repeat_ngram_size``,
   ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
-  ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``mxfp4_prefill``, ``input_dtype``, ``input_mean``,
+  ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``mxfp4_prefill``, ``mxfp4_head``, ``input_dtype``, ``input_mean``,
   ``input_std`` (CIFAR: stage 0 takes uint8 images and normalises them by table); per node
   ``layers: [start, end]`` (inclusive, as in
   ``partitions/gpt_model_parts.py:12``) and ``device``.
@@ -270,6 +270,7 @@ class PipelineConfig:
     kv_cache_scale: str = "calibrated"        # fp8 cache: per-layer scale from the first prefill's amax, or "unit"
     fp8_prefill: str = "e4m3"                 # dtype fp8: prefill activations "e4m3" (one byte, per-row scale) or "split" (e4m3 hi + residual)
     mxfp4_prefill: str = "bf16"               # dtype mxfp4: prefill above 64 rows "bf16" (expand + bf16 GEMM) or "e4m3" (W4A8 on the codes)
+    mxfp4_head: str = "bf16"                  # dtype mxfp4: the vocabulary head "bf16" or "mxfp4" (folded MXFP4 weight, ops/w4.py head_w4)
     transport: str = "grpc"
     micro_batch_size: int = 1
     num_microbatches: int = 1
@@ -428,6 +429,11 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         raise ConfigError(f"ERROR: 'mxfp4_prefill' must be 'bf16' or 'e4m3', got {m4p!r}")
     if m4p != "bf16" and cfg.get("dtype") != "mxfp4":
         raise ConfigError(f"ERROR: 'mxfp4_prefill' {m4p!r} needs dtype 'mxfp4', got {cfg.get('dtype')!r}")
+    m4h = cfg.get("mxfp4_head", "bf16")
+    if m4h not in ("bf16", "mxfp4"):
+        raise ConfigError(f"ERROR: 'mxfp4_head' must be 'bf16' or 'mxfp4', got {m4h!r}")
+    if m4h != "bf16" and cfg.get("dtype") != "mxfp4":
+        raise ConfigError(f"ERROR: 'mxfp4_head' {m4h!r} needs dtype 'mxfp4', got {cfg.get('dtype')!r}")
     kvs = cfg.get("kv_cache_scale", "calibrated")
     if kvs not in ("calibrated", "unit"):
         raise ConfigError(f"ERROR: 'kv_cache_scale' must be 'calibrated' or 'unit', got {kvs!r}")
@@ -505,7 +511,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
     return PipelineConfig(
         nodes=nodes, model_weights=str(weights), num_parts=num_parts,
         return_to_node_id=cfg.get("return_to_node_id"), model=model, dtype=cfg.get("dtype"), kv_cache_dtype=kvd,
-        kv_cache_scale=kvs, fp8_prefill=fpp, mxfp4_prefill=m4p,
+        kv_cache_scale=kvs, fp8_prefill=fpp, mxfp4_prefill=m4p, mxfp4_head=m4h,
         transport=transport, micro_batch_size=int(cfg.get("micro_batch_size", 1)),
         num_microbatches=int(cfg.get("num_microbatches", 1)), seq_len=int(cfg.get("seq_len", 64)),
         prompt_len=cfg.get("prompt_len"), prompts=prompts, decode_steps=int(cfg.get("decode_steps", 0)),

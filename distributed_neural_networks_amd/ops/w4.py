@@ -24,6 +24,11 @@ With a caller-supplied bf16 scratch, more than 64 rows expand the weight
 (``dnn_w4_expand``) and run the bf16 tile kernels on it, with their
 folded-norm, QKV-scatter, GELU, SwiGLU and residual epilogues unchanged: the
 prefill route, and the only one above 256 rows.
+
+A vocabulary head (``fold_norm(quant="mxfp4")`` of ``lm_head``) at up to 64 rows
+runs ``head_w4`` (``dnn_gemm_w4_head``, ``csrc/kernels/gemm_w4_head.h``):
+persistent workgroups with the activations in LDS, and optionally the greedy
+argmax's first pass in the epilogue.
 """
 from __future__ import annotations
 
@@ -256,3 +261,53 @@ def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = No
     check(fn(ptr(x), x.stride(0), ptr(w.q), ptr(w.scales), ptr(out), out.stride(0), ptr(bias), ptr(residual),
              0 if residual is None else residual.stride(0), M, N, K, act, norm, ptr(colsum), eps, stream_ptr()), name)
     return out
+
+
+def head_w4(x: torch.Tensor, f, logits: torch.Tensor, part: Optional[torch.Tensor] = None,
+            ids_out: Optional[torch.Tensor] = None, also: Optional[torch.Tensor] = None,
+            advance: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MXFP4 vocabulary head (``dnn_gemm_w4_head``): ``logits = linear(norm(x), W)``
+    for the folded-norm ``gemm.FoldedLinear`` ``f`` holding an ``Mxfp4Weight``, at
+    1..64 rows, in one launch.  With ``part`` (contiguous int32, >= 2 *
+    ``gemm.HEAD_PART_PER_ROW`` * M entries) every workgroup also writes its
+    argmax per row of the rounded logits there, and a second launch
+    (``argmax_final``) writes the ids to ``ids_out`` and does the decode step
+    tail as ``gemm.head_argmax`` (``also``, ``hist[row, advance]``, ``advance +=
+    1``).  Without ``part``: the logits only (sampled, penalised and constrained
+    steps).  Returns ``logits``."""
+    from .gemm import HEAD_PART_PER_ROW
+    w = f.w
+    M, K = x.shape
+    N = w.n
+    if not isinstance(w, Mxfp4Weight) or K != w.k:
+        raise ValueError(f"head_w4: x {tuple(x.shape)} vs weight {getattr(w, 'shape', None)}")
+    if x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise TypeError("head_w4: bf16 activations with a contiguous last dim")
+    if not 1 <= M <= W4_MAX_M:
+        raise ValueError(f"head_w4: 1..{W4_MAX_M} rows, got {M}")
+    if logits.dtype != torch.bfloat16 or logits.stride(1) != 1 or logits.shape[0] < M or logits.shape[1] < N:
+        raise ValueError("head_w4: bad logits buffer")
+    if f.bias is not None and f.bias.dtype != torch.float32:
+        raise TypeError("head_w4: bias must be fp32")
+    hist_ld = 0
+    if part is None:
+        if any(t is not None for t in (ids_out, also, advance, hist)):
+            raise ValueError("head_w4: ids_out / also / advance / hist need part")
+    else:
+        if part.dtype != torch.int32 or not part.is_contiguous() or part.numel() < 2 * HEAD_PART_PER_ROW * M:
+            raise ValueError(f"head_w4: part must be contiguous int32 with >= {2 * HEAD_PART_PER_ROW * M} entries")
+        if ids_out is None:
+            raise ValueError("head_w4: part needs ids_out")
+        for t, nm in ((ids_out, "ids_out"), (also, "also"), (advance, "advance")):
+            if t is not None and (t.dtype != torch.int32 or t.numel() < M or not t.is_contiguous()):
+                raise ValueError(f"head_w4: {nm} must be contiguous int32 with >= {M} entries")
+        from .transformer_ops import check_hist
+        hist_ld = check_hist(hist, advance, M, "head_w4")
+    S = lib().gemm_w4_head(ptr(x), x.stride(0), ptr(w.q), ptr(w.scales), ptr(logits), logits.stride(0), ptr(f.bias),
+                           M, N, K, f.norm, ptr(f.colsum), f.eps, ptr(part), HEAD_PART_PER_ROW, stream_ptr())
+    if S <= 0:
+        raise RuntimeError(f"gemm_w4_head failed ({S})")
+    if part is not None:
+        check(lib().argmax_final(ptr(part), S, M, ptr(ids_out), ptr(also), ptr(advance), stream_ptr(), ptr(hist),
+                                 hist_ld), "argmax_final")
+    return logits

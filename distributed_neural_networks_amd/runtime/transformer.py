@@ -23,7 +23,9 @@ decode as weight-only fp8 (W8A16, the weight bytes halve and the fused
 pre-norm stays) — GPT-2 XL config, and Llama-3 8B with ``dtype: fp8``.
 With ``w4=True`` (``dtype: "mxfp4"``) every layer projection is held only as an
 OCP MXFP4 weight (ops/w4.py: e2m1 codes, one e8m0 scale per 32 k, 4.25 bits per
-weight); embeddings and the vocabulary head stay bf16.  Steps of up to 64 rows
+weight); embeddings stay bf16, and so does the vocabulary head unless
+``mxfp4_head="mxfp4"`` holds it as the folded MXFP4 weight too (``_head_w4``).
+Steps of up to 64 rows
 run the W4A16 decode kernel, so a decode graph holds no other projection
 kernel; steps of more rows (prefill, chunked prefill, decode microbatches
 above 64 rows) expand each projection into the stage's one bf16 scratch and
@@ -45,6 +47,7 @@ from ..models.llama3 import rope_tables
 from ..ops import gemm as G_
 from ..ops.fp8 import mx_ok as fp8_mx_ok
 from ..ops import transformer_ops as T_
+from ..ops.w4 import W4_MAX_M, W4_MID_MAX_M, head_w4
 from ..ops.gemm import (ACT_GELU, ACT_NONE, ACT_SILU_MUL, HEAD_PART_PER_ROW, decode_workspace, fold_norm, head_argmax,
                         linear, linear_norm,
                         pack_gate_up, qkv_scatter_norm, skinny_rows)
@@ -93,7 +96,7 @@ class TransformerStage(StageCompute):
                  kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
                  top_p: float = 1.0, min_p: float = 0.0, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0, stop=None,
-                 constraints=None, w4: bool = False, mxfp4_prefill: str = "bf16"):
+                 constraints=None, w4: bool = False, mxfp4_prefill: str = "bf16", mxfp4_head: str = "bf16"):
         info = model_info(model)
         if w4 and fp8:
             raise ValueError("w4 (MXFP4 weights) and fp8 weights exclude each other")
@@ -106,6 +109,14 @@ class TransformerStage(StageCompute):
         if mxfp4_prefill != "bf16" and not w4:
             raise ValueError("mxfp4_prefill 'e4m3' needs MXFP4 weights (dtype mxfp4)")
         self.mxfp4_prefill = mxfp4_prefill
+        # MXFP4 weights, the vocabulary head: "bf16" (default) = the bf16 folded head; "mxfp4" = the last
+        # stage holds ln_f + lm_head only as a folded MXFP4 weight (ops/w4.py head_w4 at up to 64 rows)
+        if mxfp4_head not in ("bf16", "mxfp4"):
+            raise ValueError(f"mxfp4_head {mxfp4_head!r}: bf16 or mxfp4")
+        if mxfp4_head != "bf16" and not w4:
+            raise ValueError("mxfp4_head 'mxfp4' needs MXFP4 weights (dtype mxfp4)")
+        self.mxfp4_head = mxfp4_head
+        self.head_w4 = mxfp4_head == "mxfp4" and bool(last)  # this stage holds an MXFP4 head
         # fp8 weights, prefill (W8A8) activations: "e4m3" (default) = one e4m3
         # byte per activation, per-row scale, at the fp8 MFMA rate; "split" =
         # e4m3 hi + e4m3 residual planes against [W | W/16] (ops/fp8.py
@@ -191,6 +202,8 @@ class TransformerStage(StageCompute):
         if self.w4:
             big = max(w.n * w.k for L in self.layers
                       for w in (L.w_qkv.w, L.w_o, L.w_up.w, L.w_down))
+            if self.head_w4:  # all-position logits of more than 256 rows expand the head too
+                big = max(big, sd["lm_head.weight"].shape[0] * sd["lm_head.weight"].shape[1])
             self.w4_scratch = torch.empty((big,), dtype=torch.bfloat16, device=dev)
         if first:
             if self.family == "gpt2":
@@ -204,7 +217,7 @@ class TransformerStage(StageCompute):
                 self.lnf_w, self.lnf_b = _f32(sd["norm.weight"], dev), None
             if self.fuse_norm:
                 self.w_head = fold_norm(sd["lm_head.weight"], self.lnf_w, self.lnf_b, None, self.rms, self.eps, dev,
-                                        self.fp8)
+                                        self.fp8, quant="mxfp4" if self.head_w4 else None)
             else:
                 self.w_head = self._w(sd["lm_head.weight"])
         # decode copies of every projection in the skinny GEMM's fragment order
@@ -890,8 +903,13 @@ class TransformerStage(StageCompute):
             x_last = torch.as_strided(src, (rows, d), (ldx, 1))
             dst = out if out is not None else self.next_ids[r0:r0 + rows]
             also, adv, hist = _advance3(advance)
-            if head_argmax(x_last, self.w_head, logits[:, :self.V], self.head_part[r0 * 2 * HEAD_PART_PER_ROW:], dst,
-                           also, adv, hist):
+            part = self.head_part[r0 * 2 * HEAD_PART_PER_ROW:]
+            if self.head_w4 and rows <= W4_MAX_M:
+                fused = True
+                head_w4(x_last, self.w_head, logits[:, :self.V], part, dst, also, adv, hist)
+            else:
+                fused = head_argmax(x_last, self.w_head, logits[:, :self.V], part, dst, also, adv, hist)
+            if fused:
                 if lpn:  # the head wrote the logits too
                     self._record_logprobs(logits, dst, b0, rows, T, adv if adv is not None else lp_pos, adv is not None)
                 if stp:
@@ -899,8 +917,14 @@ class TransformerStage(StageCompute):
                 return StageOutput(logits[:, :self.V], dst)
         if self.fuse_norm:
             x_last = torch.as_strided(src, (rows, d), (ldx, 1))
-            linear_norm(x_last, self.w_head, out=logits[:, :self.V], std_buf=self.buf_lnf[r0:], ones=self.ones,
-                        q8=q8, s8=s8, ws=gws)
+            if self.head_w4 and rows <= W4_MAX_M:
+                head_w4(x_last, self.w_head, logits[:, :self.V])  # the logits only
+            elif self.head_w4:  # 65..256 rows: dnn_gemm_w4_mid on the codes; more: expand + the bf16 linear_norm
+                linear_norm(x_last, self.w_head, out=logits[:, :self.V], std_buf=self.buf_lnf[r0:], ones=self.ones,
+                            scratch=self.w4_scratch if rows > W4_MID_MAX_M else None)
+            else:
+                linear_norm(x_last, self.w_head, out=logits[:, :self.V], std_buf=self.buf_lnf[r0:], ones=self.ones,
+                            q8=q8, s8=s8, ws=gws)
         else:
             lnf = self.buf_lnf[r0:r0 + rows]
             T_.layernorm(src, self.lnf_w, self.lnf_b, lnf, self.eps, self.rms, rows=rows, ldx=ldx)
@@ -1007,7 +1031,7 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                        kv_scale: str = "calibrated", fp8_prefill: str = "e4m3", top_p: float = 1.0,
                        min_p: float = 0.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                        frequency_penalty: float = 0.0, logprobs: int = 0, stop=None, constraints=None,
-                       mxfp4_prefill: str = "bf16"):
+                       mxfp4_prefill: str = "bf16", mxfp4_head: str = "bf16"):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
     w4 = dtype == "mxfp4"
     info = model_info(model)
@@ -1017,7 +1041,7 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                             top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                             logprobs=logprobs, stop=stop, constraints=constraints, w4=w4,
-                            mxfp4_prefill=mxfp4_prefill)
+                            mxfp4_prefill=mxfp4_prefill, mxfp4_head=mxfp4_head)
 
 
 # ---------------------------------------------------------------------- smoke / golden check

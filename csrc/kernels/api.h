@@ -218,6 +218,13 @@ int dnn_gemm_w4(const void* A, int lda, const void* Wq, const void* Ws, void* C,
 int dnn_gemm_w4_mid(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
                     const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
                     hipStream_t st);
+// dnn_gemm_w4_mn (gemm_w4_mn.h): the contract and returns of dnn_gemm_w4_mid, 1 <= M <= 256, for projections too
+// narrow to fill the device with one workgroup per 64 columns: a grid of ceil(N / 32) x ceil(M / 64) workgroups
+// (every M block reads the codes again, from L2), the waves of a workgroup split K by chunk parity and meet in
+// LDS in a fixed order (no atomics: the same bits on every launch).  ops/w4.py w4_mn_ok states its shapes.
+int dnn_gemm_w4_mn(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
+                   const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
+                   hipStream_t st);
 int dnn_w4_expand(const void* Wq, const void* Ws, void* W, int ldw, int N, int K, hipStream_t st);
 // dnn_gemm_w4_head (gemm_w4_head.h): the MXFP4 vocabulary head, 1 <= M <= 64: bf16 logits C = norm-folded
 // A . dq(W)^T + bias from persistent workgroups (at most one per CU, A in LDS), and with part != nullptr each

@@ -251,6 +251,7 @@ __global__ __launch_bounds__(512) void gemm_w4_kernel(const uint8_t* __restrict_
 }  // namespace dnn
 
 #include "gemm_w4_mid.h"  // dnn_gemm_w4_mid's kernel: up to 256 rows, A shared through LDS
+#include "gemm_w4_mn.h"   // dnn_gemm_w4_mn's kernel: up to 256 rows on narrow projections, an M x N grid, waves split K
 #include "gemm_w4a8.h"    // dnn_gemm_w4a8: prefill on MX e4m3 activations, the codes on the scaled MFMA
 #include "gemm_w4_head.h"  // dnn_gemm_w4_head: the vocabulary head, persistent workgroups, argmax partials
 
@@ -394,6 +395,47 @@ extern "C" int dnn_gemm_w4_mid(const void* A, int lda, const void* Wq, const voi
     case ACT_RELU: return launch_w4_mid_norm<ACT_RELU>(norm, W4_ARGS);
     case ACT_GELU: return launch_w4_mid_norm<ACT_GELU>(norm, W4_ARGS);
     default: return launch_w4_mid_norm<ACT_SILU_MUL>(norm, W4_ARGS);
+  }
+#undef W4_ARGS
+}
+
+// dnn_gemm_w4_mn: one workgroup per 64 rows x 32 columns, its waves split K by chunk parity (gemm_w4_mn.h).
+template <int ACT>
+static int launch_w4_mn(int norm, const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc,
+                        const float* bias, const void* R, int ldr, int M, int N, int K, const float* colsum, float eps,
+                        hipStream_t st) {
+  const dim3 grid(((N + 15) / 16 + 1) / 2, (M + W4N_BM - 1) / W4N_BM);
+#define W4N_LAUNCH(NORM)                                                                                         \
+  hipLaunchKernelGGL((gemm_w4_mn_kernel<ACT, NORM>), grid, dim3(256), W4N_LDS, st, (const uint8_t*)A, lda * 2, \
+                     (const uint8_t*)Wq, (const uint8_t*)Ws, (bf16_t*)C, ldc, bias, (const bf16_t*)R, ldr, M, N, K, \
+                     colsum, eps)
+  switch (norm) {
+    case W4_NORM_NONE: W4N_LAUNCH(W4_NORM_NONE); break;
+    case W4_NORM_RMS: W4N_LAUNCH(W4_NORM_RMS); break;
+    default: W4N_LAUNCH(W4_NORM_LN); break;
+  }
+#undef W4N_LAUNCH
+  return (int)hipGetLastError();
+}
+
+extern "C" int dnn_gemm_w4_mn(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc,
+                              const float* bias, const void* R, int ldr, int M, int N, int K, int act, int norm,
+                              const float* colsum, float eps, hipStream_t st) {
+  if (A == nullptr || Wq == nullptr || Ws == nullptr || C == nullptr) return -1;
+  if (norm == W4_NORM_LN && colsum == nullptr) return -1;
+  if (M < 1 || M > 256) return -2;
+  if (N < 1 || K < 32 || K % 32 != 0 || act < ACT_NONE || act > ACT_SILU_MUL || norm < 0 || norm > W4_NORM_LN ||
+      (act == ACT_SILU_MUL && N % 16 != 0))
+    return -3;
+  const int NO = act == ACT_SILU_MUL ? N / 2 : N;
+  if (ldc < NO || lda < K || (R != nullptr && ldr < NO)) return -4;
+  if ((((uintptr_t)A | (uintptr_t)Wq) & 15) != 0 || (lda & 7) != 0) return -5;
+#define W4_ARGS A, lda, Wq, Ws, C, ldc, bias, R, ldr, M, N, K, colsum, eps, st
+  switch (act) {
+    case ACT_NONE: return launch_w4_mn<ACT_NONE>(norm, W4_ARGS);
+    case ACT_RELU: return launch_w4_mn<ACT_RELU>(norm, W4_ARGS);
+    case ACT_GELU: return launch_w4_mn<ACT_GELU>(norm, W4_ARGS);
+    default: return launch_w4_mn<ACT_SILU_MUL>(norm, W4_ARGS);
   }
 #undef W4_ARGS
 }

@@ -20,6 +20,9 @@ Code ``c``: bit 3 = sign, bits 0..2 index (0, 0.5, 1, 1.5, 2, 3, 4, 6).
 Decode-sized M (<= 64) runs ``dnn_gemm_w4``.  65..256 rows without a scratch
 run ``dnn_gemm_w4_mid`` (``csrc/kernels/gemm_w4_mid.h``: the codes are read
 once, A is shared through LDS, nothing is expanded): the decode microbatches.
+Projections too narrow for its N / 64 workgroups run ``dnn_gemm_w4_mn``
+(``csrc/kernels/gemm_w4_mn.h``: workgroups tile M and N, their waves split K;
+``linear_w4(mn=True)``, the shapes of ``w4_mn_ok``).
 With a caller-supplied bf16 scratch, more than 64 rows expand the weight
 (``dnn_w4_expand``) and run the bf16 tile kernels on it, with their
 folded-norm, QKV-scatter, GELU, SwiGLU and residual epilogues unchanged: the
@@ -58,6 +61,32 @@ def w4_mid_ok(M: int, N: int, K: int) -> bool:
     if N * K <= 1 << 20:
         return True
     return N >= 4096 and not (N >= 16384 and M > 128)
+
+
+def w4_mn_ok(M: int, N: int, K: int) -> bool:
+    """Whether a decode step of 65..256 rows runs ``dnn_gemm_w4_mn`` on this
+    projection, ahead of both ``dnn_gemm_w4_mid`` and the expansion
+    (bench/probes/w4_mn_ab.py, profiles/w4_mn_ab.jsonl: three arms, 5 rounds,
+    us per launch at 96 / 128 / 256 rows, mn | mid | expand + bf16 GEMM):
+      768 -> 768     6.6 /  6.6 /  6.7 | 10.2 / 12.1 /  18.7 |  9.0 /  9.0 /  11.0
+      768 -> 2304    6.8 /  6.8 /  8.2 | 10.4 / 12.2 /  18.9 | 11.2 / 13.2 /  17.5
+      768 -> 3072    6.8 /  6.8 /  8.3 | 10.4 / 12.2 /  19.0 | 13.8 / 13.9 /  20.2
+      3072 -> 768   16.7 / 16.9 / 16.8 | 28.7 / 35.1 /  58.5 | 17.7 / 17.7 /  23.2
+      1280 -> 3840   9.1 /  9.2 / 11.8 | 14.5 / 17.3 /  27.9 | 20.3 / 23.8 /  37.3
+      1600 -> 1600  11.3 / 11.3 / 11.9 | 17.7 / 21.2 /  34.3 | 16.9 / 17.0 /  26.0
+      6400 -> 1600  32.1 / 32.3 / 34.7 | 55.8 / 68.8 / 116.6 | 47.8 / 47.6 /  76.3
+      1600 -> 4800  12.9 / 15.1 / 24.0 | 17.8 / 21.2 /  34.4 | 31.3 / 35.8 /  58.6
+      4096 -> 6144  24.9 / 28.9 / 47.4 | 37.4 / 46.0 /  76.7 | 74.1 / 83.4 / 142.5
+    In all 27 cases the slowest mn round is faster than the fastest round of
+    both other arms (the spread between rounds of one arm is below 2 %; the
+    narrowest margin, 3072 -> 768 at 96 rows, is 16.73 against 17.65), the two
+    guard shapes that the mid kernel held included, and 768 -> 768, a weight
+    of at most 1 Mi elements, too.  The rule is the box those shapes span:
+    N <= 6144 and K <= 6400.  Wider or deeper projections (Llama-3 8B gate|up
+    and down, any vocabulary head) are not measured and stay where
+    ``w4_mid_ok`` puts them: every workgroup of this kernel reads 64 rows of A
+    per 32 columns, N / 32 x M x 2 K bytes from L2, which grows with N x K."""
+    return W4_MAX_M < M <= W4_MID_MAX_M and N <= 6144 and K <= 6400
 
 
 def _table(device) -> torch.Tensor:
@@ -226,14 +255,16 @@ def linear_w4a8(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = 
 def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = None, act: int = 0,
               residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, norm: int = 0,
               colsum: Optional[torch.Tensor] = None, eps: float = 0.0, scratch: Optional[torch.Tensor] = None,
-              std_buf: Optional[torch.Tensor] = None, ones: Optional[torch.Tensor] = None) -> torch.Tensor:
+              std_buf: Optional[torch.Tensor] = None, ones: Optional[torch.Tensor] = None,
+              mn: bool = False) -> torch.Tensor:
     """bf16 x (M, K) times an MXFP4 weight, bf16 out.  ``norm`` (1 RMS / 2 LN,
     with ``colsum`` for LN) is a folded pre-norm (``gemm.fold_norm(quant="mxfp4")``).
     M <= 64: one ``dnn_gemm_w4`` launch.  M > 64 with ``scratch`` (bf16, >= N K
     elements): the weight is expanded into it and the bf16 ``gemm.linear`` /
     ``gemm.linear_norm`` run on it (``std_buf`` / ``ones`` as ``linear_norm``).
     65 <= M <= 256 without a scratch: one ``dnn_gemm_w4_mid`` launch on the
-    codes.  More than 256 rows need the scratch."""
+    codes, or with ``mn`` one ``dnn_gemm_w4_mn`` launch (the M x N grid for
+    narrow projections, ``w4_mn_ok``).  More than 256 rows need the scratch."""
     M, K = x.shape
     N = w.n
     if K != w.k:
@@ -257,7 +288,12 @@ def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = No
         raise TypeError("linear_w4: bias must be fp32")
     if residual is not None and (residual.shape[0] < M or residual.stride(1) != 1):
         raise ValueError("linear_w4: bad residual")
-    fn, name = (lib().gemm_w4, "gemm_w4") if M <= W4_MAX_M else (lib().gemm_w4_mid, "gemm_w4_mid")
+    if M <= W4_MAX_M:
+        fn, name = lib().gemm_w4, "gemm_w4"
+    elif mn:
+        fn, name = lib().gemm_w4_mn, "gemm_w4_mn"
+    else:
+        fn, name = lib().gemm_w4_mid, "gemm_w4_mid"
     check(fn(ptr(x), x.stride(0), ptr(w.q), ptr(w.scales), ptr(out), out.stride(0), ptr(bias), ptr(residual),
              0 if residual is None else residual.stride(0), M, N, K, act, norm, ptr(colsum), eps, stream_ptr()), name)
     return out

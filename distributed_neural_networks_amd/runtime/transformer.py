@@ -674,7 +674,8 @@ class TransformerStage(StageCompute):
             from ..ops.w4 import linear_w4, linear_w4a8
             if self._w4_a8:  # W4A8 prefill piece: quantise pass + the codes on the scaled MFMA
                 return linear_w4a8(x, w, b, act, residual, out, self.q8, self.sx8), False
-            return linear_w4(x, w, b, act, residual, out, scratch=self._w4_scratch_for(x.shape[0], w)), False
+            return linear_w4(x, w, b, act, residual, out, scratch=self._w4_scratch_for(x.shape[0], w),
+                             mn=self._w4_mn(x.shape[0], w)), False
         if self.fp8:
             from ..ops.fp8 import linear_fp8, linear_w8
             if skinny_rows(x.shape[0], w.q.shape[0], w8=True):  # decode: weight-only fp8 (bf16 activations)
@@ -689,12 +690,19 @@ class TransformerStage(StageCompute):
     def _w4_scratch_for(self, rows: int, w):
         """The expand scratch where this step expands the MXFP4 weight ``w``
         (prefill pieces of more than 64 rows, steps above 256 rows, and the
-        shapes ``w4_mid_ok`` leaves to the expansion), else None: the W4A16
-        kernels run on the codes."""
-        from ..ops.w4 import W4_MAX_M, w4_mid_ok
-        if rows <= W4_MAX_M or self._w4_a8 or (self._w4_decode and w4_mid_ok(rows, w.n, w.k)):
+        decode shapes neither ``w4_mid_ok`` nor ``w4_mn_ok`` takes), else None:
+        the W4A16 kernels run on the codes."""
+        from ..ops.w4 import W4_MAX_M, w4_mid_ok, w4_mn_ok
+        if rows <= W4_MAX_M or self._w4_a8 or (self._w4_decode and (w4_mid_ok(rows, w.n, w.k) or
+                                                                    w4_mn_ok(rows, w.n, w.k))):
             return None
         return self.w4_scratch
+
+    def _w4_mn(self, rows: int, w) -> bool:
+        """MXFP4 stage, a decode step of 65..256 rows on a projection of
+        ``w4_mn_ok``: ``linear_w4`` runs ``dnn_gemm_w4_mn``, not the mid kernel."""
+        from ..ops.w4 import w4_mn_ok
+        return bool(self.w4 and self._w4_decode and not self._w4_a8 and w4_mn_ok(rows, w.n, w.k))
 
     def _w4x(self, f, rows: int):
         """MXFP4 stage, a step that expands (``_w4_scratch_for``): the
@@ -798,7 +806,8 @@ class TransformerStage(StageCompute):
                 pass  # prefill (no RoPE): c_attn wrote q head-major and K / V straight into the caches
             elif self.fuse_norm:
                 qkv = linear_norm(h_in, w_qkv, out=self.buf_qkv[r0:r1], std_buf=a, ones=self.ones, q8=q8,
-                                  s8=s8, ws=gws, rs_in=rs if have_rs else None, sx=self.sx8 if a8 else None)
+                                  s8=s8, ws=gws, rs_in=rs if have_rs else None, sx=self.sx8 if a8 else None,
+                                  mn=self._w4_mn(ntok, L.w_qkv.w))
             else:
                 T_.layernorm(h_in, L.ln1_w, L.ln1_b, a, self.eps, self.rms, rows=ntok)
                 qkv, _ = self._lin(a, L.w_qkv, L.b_qkv, out=self.buf_qkv[r0:r1])
@@ -822,7 +831,7 @@ class TransformerStage(StageCompute):
                     mx_f = (self.q8b, self.sx8b)
                 f = linear_norm(h, self._w4x(L.w_up, ntok), act=up_act, out=self.buf_f[r0:r1], std_buf=a, ones=self.ones, q8=q8,
                                 s8=s8, ws=gws, rs_in=rs if have_rs else None,
-                                sx=self.sx8 if T > 1 else None, q_out=mx_f)
+                                sx=self.sx8 if T > 1 else None, q_out=mx_f, mn=self._w4_mn(ntok, L.w_up.w))
                 if mx_f is not None:
                     f = self.buf_f[r0:r1]  # shape only: c_proj reads the e4m3 bytes in mx_f
             else:

@@ -211,6 +211,13 @@ PYBIND11_MODULE(_dnn_hip, m) {
   m.def("cifar_head_tail_x3", [](u64 hid, u64 w2h, u64 w2l, u64 b2, u64 probs, u64 pred, int B, u64 st) {
     return dnn_cifar_head_tail_x3(CFP(hid), CP(w2h), CP(w2l), CFP(b2), FP(probs), IP(pred), B, ST(st));
   });
+  m.def("cifar_fc1_head_x3", [](u64 a, int lda, u64 wh, u64 wl, int ldw, u64 b1, u64 w2h, u64 w2l, u64 b2, u64 part,
+                                u64 probs, u64 pred, int M, int N, int K, u64 st, int split_in) {
+    return dnn_cifar_fc1_head_x3(CFP(a), lda, CP(wh), CP(wl), ldw, CFP(b1), CP(w2h), CP(w2l), CFP(b2), FP(part),
+                                 FP(probs), IP(pred), M, N, K, ST(st), split_in);
+  }, py::arg("a"), py::arg("lda"), py::arg("wh"), py::arg("wl"), py::arg("ldw"), py::arg("b1"), py::arg("w2h"),
+        py::arg("w2l"), py::arg("b2"), py::arg("part"), py::arg("probs"), py::arg("pred"), py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("st"), py::arg("split_in") = 0);
   m.def("cifar_head_tail", [](u64 hid, u64 w2p, u64 b2, u64 probs, u64 pred, int B, u64 st) {
     return dnn_cifar_head_tail(CP(hid), CP(w2p), CFP(b2), FP(probs), IP(pred), B, ST(st));
   });

@@ -107,6 +107,13 @@ int dnn_cifar_fc1_get_sched();
 int dnn_cifar_split_blocked(const float* a, float* o, int M, int K, int dir, hipStream_t st);
 int dnn_cifar_head_tail_x3(const float* hid, const void* w2h, const void* w2l, const float* b2, float* probs, int* pred,
                            int B, hipStream_t st);
+// fp32 units 2-3 in two launches: fc1 (as dnn_cifar_fc1_x3) with fc2 in its epilogue, then bias + softmax + argmax
+// (as dnn_cifar_head_tail_x3); the hidden rows are never stored.  part: workspace [2][M][16] fp32.  Negative =
+// rejected, nothing launched: -1 K < 32, K % 32, lda % 4 or ldw % 8; -2 N != 512; -3 a null pointer (part, A, W,
+// w2, b2, probs, pred); -4 M < 1; -5 part, w2h or w2l not 16-byte aligned.
+int dnn_cifar_fc1_head_x3(const float* A, int lda, const void* Wh, const void* Wl, int ldw, const float* b1,
+                          const void* w2h, const void* w2l, const float* b2, float* part, float* probs, int* pred, int M,
+                          int N, int K, hipStream_t st, int split_in = 0);
 int dnn_cifar_head_tail(const void* hid, const void* w2p, const float* b2, float* probs, int* pred, int B,
                         hipStream_t st);
 // split: rows of 2 kpad bytes, e4m3 hi plane then the residual plane (W8A8 prefill with split activations)

@@ -90,6 +90,15 @@
 //    non-MFMA vector instructions per k-step instead of 207; the same schedule
 //    with scalar conversions and per-segment addressing stays compiled as the
 //    A/B's other arm (dnn_cifar_fc1_set_sched: 1 staggered, 2 lean).
+//    With the template parameter HEAD (dnn_cifar_fc1_head_x3: units 2-3 in one
+//    stage at large batch) fc2 runs in the epilogue on the accumulators as they
+//    stand, 48 more MFMAs per wave; the four waves of a row group add their
+//    partial logits through LDS and the workgroup writes 16 floats per row to
+//    part[column tile][M][16] instead of 256 hidden values (8 MiB instead of
+//    128 MiB written and read back at B = 65536).  No cross-workgroup
+//    synchronisation; the summation order is fixed and documented at the kernel.
+//  * cifar_head_finish_x3_kernel: (part[0] + part[1]) + bias, softmax, argmax:
+//    the tail of the HEAD path, the head kernel's lines after its MFMAs.
 //  * cifar_split3_kernel: fp32 (B,K) -> bf16 (B,3K) = [hi | hi | lo], the A
 //    operand of the small-batch fc1 (one skinny bf16 GEMM over K' = 3K against
 //    W' = [W_hi | W_lo | W_hi]) when the 256^2 tiles cannot fill the chip.
@@ -932,12 +941,59 @@ __device__ __forceinline__ void f1_tile_coords(int logical, int ntm, int ntn, in
 // v_cvt_pk_bf16_f32: the same instruction and rounding on the same values, so
 // the outputs are bitwise those of the other arm.  Measured in
 // profiles/cifar_lean_after.md: fc1 0.646 -> 0.572 ms interleaved, every round.
-template <bool SPLIT_IN, bool LEAN>
+//
+// HEAD: fc2 runs in the epilogue and the hidden tile is never stored (units 2-3
+// in two launches, see cifar_head_finish_x3_kernel).  The k loop is the one
+// above, unchanged.  After it a wave holds relu(fc1) for 128 rows x 64 hidden
+// columns in its accumulators, and that layout is an MFMA operand as it stands:
+// sub-tile (i, j) gives lane l the row m = i*16 + (l & 15) and the hidden
+// columns j*16 + 4*(l >> 4) + r, r = 0..3, which is how mfma_f32_16x16x16 lays
+// out its B operand (column l & 15, k = 4*(l >> 4) + r).  Two adjacent j fill
+// the eight k slots of one mfma_f32_16x16x32_bf16 B operand: lane group
+// g = l >> 4, slot s holds hidden column (2p + (s >> 2))*16 + 4g + (s & 3) of
+// the pair p, and fc2's weights are loaded in the same (g, s) order as the A
+// operand (row = class l & 15, padded to 16), so the permutation of k inside a
+// block of 32 cancels.  Per 16 rows: bias + ReLU in fp32 as epi_t4<ACT_RELU>
+// computes them, split2 into bf16 hi / lo, and per pair the three terms in the
+// head kernel's order, hid_hi w_hi, hid_hi w_lo, hid_lo w_hi, accumulated in
+// fp32 into logits^T[class 4*(l >> 4) + r][row l & 15]: 48 MFMAs per wave.
+// Summation order of a logit (fixed, so two runs are bitwise equal; it is a
+// reassociation of the unfused head's single chain over k = 0..511):
+//   1. inside a wave, one chain over its 64 hidden columns, pair 0 then pair 1,
+//      three terms each, the 32 k of a term summed by the MFMA;
+//   2. the four waves of a row group (wc = 0..3, hidden columns wc*64..+63 of
+//      the tile) through LDS, ((p0 + p1) + p2) + p3, which is part[tn][m][class];
+//   3. cifar_head_finish_x3_kernel: (part[0] + part[1]) + bias.
+// No atomics, tickets or fences: a workgroup writes its own rows of its own
+// tn plane.  LDS is free once group 0 has passed its last barrier (group 1's
+// last fragment reads were retired by the lgkmcnt(0) ahead of that barrier,
+// and no DMA is in flight); every wave then writes its partial, passes one
+// more barrier (1 + 2 nk + 1 for any nk >= 1, both groups) and reduces two of
+// the row group's eight 16-row blocks.  Rows past M are computed (from zeros or
+// the clamped row) and never stored.
+template <bool HEAD>
+struct F1Head {
+  // Zero bytes of kernel arguments: the plain instantiations keep their 72-byte layout and their
+  // descriptors.  This leans on two things a compiler update may change: the zero-length array is
+  // a GNU extension (sizeof == 0), and clang lowers the empty aggregate to a by-value argument
+  // of size 0 at offset 72.  tools/compare_kernel_asm.py old.s new.s --rule
+  // 'cifar_fc1_x3_kernel=a[:2]' shows it (.amdhsa_kernarg_size 72); an empty struct {} costs 4
+  // bytes of kernarg and nothing else, and is the fallback should this stop compiling.
+  char none[0];
+};
+template <>
+struct F1Head<true> {
+  const bf16_t* w2h;  // fc2 hi / lo, bf16 [16][512], classes 10..15 zero
+  const bf16_t* w2l;
+  float* part;  // [N / 256][M][16] fp32
+};
+
+template <bool SPLIT_IN, bool LEAN, bool HEAD = false>
 __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __restrict__ A, int lda,
                                                               const bf16_t* __restrict__ Wh,
                                                               const bf16_t* __restrict__ Wl, int ldw,
                                                               const float* __restrict__ bias, float* __restrict__ C,
-                                                              int ldc, int M, int N, int K) {
+                                                              int ldc, int M, int N, int K, F1Head<HEAD> hd) {
   __shared__ __attribute__((aligned(1024))) char smem[2 * 4 * F1_PLANE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntn = N / F1_T, ntm = (M + F1_T - 1) / F1_T;
@@ -1217,6 +1273,70 @@ __global__ __launch_bounds__(512, 1) void cifar_fc1_x3_kernel(const float* __res
     if (!g1 || t + 1 < nk) barrier();
   }
 
+  if constexpr (HEAD) {
+    // the lane map again from an opaque copy of tid, so that nothing but tid lives across the k loop
+    int et = tid;
+    asm volatile("" : "+v"(et));
+    const int el = et & 63, ew = et >> 6, efr = el & 15, efc = el >> 4, ewr = ew >> 2, ewc = ew & 3;
+    // fc2 fragments of this wave's 64 hidden columns, in the accumulators' k order, and its fc1 bias
+    const int nw = n0 + ewc * 64 + efc * 4;
+    bf16x8 w2fh[2], w2fl[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int o = efr * 512 + nw + p * 32;
+      const uint2 h0 = *reinterpret_cast<const uint2*>(hd.w2h + o), h1 = *reinterpret_cast<const uint2*>(hd.w2h + o + 16);
+      const uint2 l0 = *reinterpret_cast<const uint2*>(hd.w2l + o), l1 = *reinterpret_cast<const uint2*>(hd.w2l + o + 16);
+      w2fh[p] = __builtin_bit_cast(bf16x8, uint4{h0.x, h0.y, h1.x, h1.y});
+      w2fl[p] = __builtin_bit_cast(bf16x8, uint4{l0.x, l0.y, l1.x, l1.y});
+    }
+    f32x4 bv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) bv[j][r] = bias != nullptr ? bias[nw + j * 16 + r] : 0.f;
+    f32x4 lg[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      f32x4 v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[j] = acc[i][j];
+        if (bias != nullptr) v[j] += bv[j];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[j][r] = fmaxf(v[j][r], 0.f);
+      }
+      lg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        uint4 hi, lo;
+        split2<true>(v[2 * p][0], v[2 * p][1], hi.x, lo.x);
+        split2<true>(v[2 * p][2], v[2 * p][3], hi.y, lo.y);
+        split2<true>(v[2 * p + 1][0], v[2 * p + 1][1], hi.z, lo.z);
+        split2<true>(v[2 * p + 1][2], v[2 * p + 1][3], hi.w, lo.w);
+        const bf16x8 hh = __builtin_bit_cast(bf16x8, hi), hl = __builtin_bit_cast(bf16x8, lo);
+        lg[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2fh[p], hh, lg[i], 0, 0, 0);
+        lg[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2fl[p], hh, lg[i], 0, 0, 0);
+        lg[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2fh[p], hl, lg[i], 0, 0, 0);
+      }
+    }
+    // partials of the 8 waves: [wave][i][lane] f32x4 = 64 KiB, lane-linear (conflict-free b128)
+    f32x4* const red = reinterpret_cast<f32x4*>(smem);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) red[(ew * 8 + i) * 64 + el] = lg[i];
+    barrier();
+    float* const part = hd.part + (size_t)tn * M * 16;
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii) {
+      const int i = ewc * 2 + ii;
+      f32x4 s = red[((ewr * 4 + 0) * 8 + i) * 64 + el];
+      s += red[((ewr * 4 + 1) * 8 + i) * 64 + el];
+      s += red[((ewr * 4 + 2) * 8 + i) * 64 + el];
+      s += red[((ewr * 4 + 3) * 8 + i) * 64 + el];
+      const int m = m0 + ewr * 128 + i * 16 + efr;
+      if (m < M) *reinterpret_cast<f32x4*>(part + (size_t)m * 16 + efc * 4) = s;
+    }
+    return;
+  }
   // epilogue (transposed accumulators): row m0 + wr*128 + i*16 + (lane & 15), cols n..n+3
   const bool vec = epi_vec_ok(C, ldc, bias, nullptr, 0);
 #pragma unroll
@@ -1336,6 +1456,51 @@ __global__ __launch_bounds__(256) void cifar_head_tail_x3_kernel(const float* __
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wfh[s], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wfl[s], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wfh[s], acc, 0, 0, 0);
+    }
+    // acc[r] = logit(row = r0 + (lane>>4)*4 + r, class = col)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float z = col < 10 ? acc[r] + bias : -INFINITY;
+      float mx = z;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      const float e = col < 10 ? expf(z - mx) : 0.f;
+      float sum = e;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, 64);
+      int cand = (z == mx) ? col : 16;  // smallest class index attaining the max (numpy semantics)
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+      const int m = r0 + (lane >> 4) * 4 + r;
+      if (m < B) {
+        if (col < 10) probs[(size_t)m * 10 + col] = e / sum;
+        if (col == 0) pred[m] = cand;
+      }
+    }
+  }
+}
+
+// The tail of the fused fc1 + fc2 (cifar_fc1_x3_kernel<.., HEAD>): part is [2][B][16] fp32, the two
+// column tiles' partial logits (classes 10..15 are zero).  Per row z = (part[0] + part[1]) + bias,
+// then the softmax, first-index argmax and stores of cifar_head_tail_x3_kernel, line for line, on
+// the same lane map (row r0 + (lane>>4)*4 + r, class lane & 15).  In this file for its IEEE expf
+// and division (see cifar_head_tail_kernel).
+__global__ __launch_bounds__(256) void cifar_head_finish_x3_kernel(const float* __restrict__ part,
+                                                                   const float* __restrict__ b2,
+                                                                   float* __restrict__ probs, int* __restrict__ pred,
+                                                                   int B) {
+  const int lane = threadIdx.x & 63;
+  const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nw = (gridDim.x * blockDim.x) >> 6;
+  const int col = lane & 15;
+  const float bias = col < 10 ? b2[col] : 0.f;
+  for (int r0 = gw * 16; r0 < B; r0 += nw * 16) {
+    f32x4 acc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = r0 + (lane >> 4) * 4 + r;
+      const size_t rc = row < B ? row : B - 1;
+      acc[r] = part[rc * 16 + col] + part[((size_t)B + rc) * 16 + col];
     }
     // acc[r] = logit(row = r0 + (lane>>4)*4 + r, class = col)
 #pragma unroll
@@ -1519,10 +1684,22 @@ static int launch_fc1_x3(const float* A, int lda, const void* Wh, const void* Wl
                          int ldc, int M, int N, int K, int blocks, hipStream_t st) {
   if (g_fc1_sched == 2)
     hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, true>), dim3(blocks), dim3(512), 0, st, A, lda,
-                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
+                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K, F1Head<false>{});
   else
     hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, false>), dim3(blocks), dim3(512), 0, st, A, lda,
-                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K);
+                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, C, ldc, M, N, K, F1Head<false>{});
+  return (int)hipGetLastError();
+}
+
+template <bool SPLIT_IN>
+static int launch_fc1_head_x3(const float* A, int lda, const void* Wh, const void* Wl, int ldw, const float* bias,
+                              F1Head<true> hd, int M, int N, int K, int blocks, hipStream_t st) {
+  if (g_fc1_sched == 2)
+    hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, true, true>), dim3(blocks), dim3(512), 0, st, A, lda,
+                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, (float*)nullptr, 0, M, N, K, hd);
+  else
+    hipLaunchKernelGGL((cifar_fc1_x3_kernel<SPLIT_IN, false, true>), dim3(blocks), dim3(512), 0, st, A, lda,
+                       (const bf16_t*)Wh, (const bf16_t*)Wl, ldw, bias, (float*)nullptr, 0, M, N, K, hd);
   return (int)hipGetLastError();
 }
 
@@ -1563,6 +1740,30 @@ extern "C" int dnn_cifar_head_tail_x3(const float* hid, const void* w2h, const v
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(cifar_head_tail_x3_kernel, dim3(blocks), dim3(256), 0, st, hid, (const bf16_t*)w2h,
                      (const bf16_t*)w2l, b2, probs, pred, B);
+  return (int)hipGetLastError();
+}
+
+// Units 2-3 at fp32 precision in two launches: fc1 with fc2 in its epilogue (partial logits to
+// part[2][M][16]), then bias + softmax + argmax.  Rejections (negative, nothing launched): api.h.
+extern "C" int dnn_cifar_fc1_head_x3(const float* A, int lda, const void* Wh, const void* Wl, int ldw,
+                                     const float* b1, const void* w2h, const void* w2l, const float* b2, float* part,
+                                     float* probs, int* pred, int M, int N, int K, hipStream_t st, int split_in) {
+  if (M < 1) return -4;
+  if (N != 2 * F1_T) return -2;
+  if (K < F1_K || K % F1_K != 0 || lda % 4 != 0 || ldw % 8 != 0) return -1;
+  if (part == nullptr || A == nullptr || Wh == nullptr || Wl == nullptr || w2h == nullptr || w2l == nullptr ||
+      b2 == nullptr || probs == nullptr || pred == nullptr)
+    return -3;
+  if ((((uintptr_t)part | (uintptr_t)w2h | (uintptr_t)w2l) & 15) != 0) return -5;
+  const F1Head<true> hd{(const bf16_t*)w2h, (const bf16_t*)w2l, part};
+  const int blocks = ((M + F1_T - 1) / F1_T) * (N / F1_T);
+  const int rc = split_in ? launch_fc1_head_x3<true>(A, lda, Wh, Wl, ldw, b1, hd, M, N, K, blocks, st)
+                          : launch_fc1_head_x3<false>(A, lda, Wh, Wl, ldw, b1, hd, M, N, K, blocks, st);
+  if (rc != 0) return rc;
+  int fblocks = ((M + 15) / 16 + 3) / 4;
+  if (fblocks > 1024) fblocks = 1024;
+  hipLaunchKernelGGL(cifar_head_finish_x3_kernel, dim3(fblocks), dim3(256), 0, st, (const float*)part, b2, probs, pred,
+                     M);
   return (int)hipGetLastError();
 }
 

@@ -432,9 +432,49 @@ def head_tail(hid: torch.Tensor, w: CifarHeadWeights, probs: Optional[torch.Tens
     return probs, pred
 
 
+HEAD_FUSION = True  # fp32, B >= FC1_X3_MIN_ROWS: fc2 in fc1's epilogue (cifar_fc1_head_x3), no hidden tensor
+
+
+def set_head_fusion(on) -> bool:
+    """Units 2-3 at fp32 precision and large batch: fc2 inside fc1's epilogue plus a finish kernel
+    (on, the default) or fc1, the hidden rows in HBM, then the head kernel (off).  Returns the
+    previous setting so callers can restore it."""
+    global HEAD_FUSION
+    prev, HEAD_FUSION = HEAD_FUSION, bool(on)
+    return prev
+
+
+def _head_fused(w: CifarHeadWeights, B: int) -> bool:
+    """Whether ``head_forward`` takes the fused path for ``B`` rows (then it needs ``part``, not ``hid``)."""
+    return HEAD_FUSION and w.precision == "fp32" and B >= FC1_X3_MIN_ROWS
+
+
 def head_forward(h: torch.Tensor, w: CifarHeadWeights, hid: Optional[torch.Tensor] = None,
                  probs: Optional[torch.Tensor] = None, pred: Optional[torch.Tensor] = None,
-                 boundary: str = "fp32") -> Tuple[torch.Tensor, torch.Tensor]:
-    """Units 2-3: h (B,4096) -> (probs (B,10) fp32, pred (B,) int32)."""
-    hid = fc1_forward(h, w, out=hid, boundary=boundary)
-    return head_tail(hid, w, probs, pred)
+                 boundary: str = "fp32", part: Optional[torch.Tensor] = None,
+                 scratch: Optional[torch.Tensor] = None,
+                 fused: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Units 2-3: h (B,4096) -> (probs (B,10) fp32, pred (B,) int32).  Fused path (``_head_fused``):
+    ``part`` is the (2,B,16) fp32 partial-logit workspace and ``hid`` is not used; otherwise
+    ``fc1_forward`` (``hid``, ``scratch``) then ``head_tail``.  ``fused``: the path, for a caller
+    that has read the switch already and sized its buffers by it (None: decided here)."""
+    B = h.shape[0]
+    if fused is None:
+        fused = _head_fused(w, B)
+    elif fused and (w.precision != "fp32" or B < FC1_X3_MIN_ROWS):
+        raise ValueError(f"head_forward: the fused path needs fp32 and B >= {FC1_X3_MIN_ROWS}, got {w.precision}, B = {B}")
+    if not fused:
+        hid = fc1_forward(h, w, out=hid, scratch=scratch, boundary=boundary)
+        return head_tail(hid, w, probs, pred)
+    split = _split_boundary(boundary, w.precision)
+    _check_act(h, (4096,), torch.float32, "fc1 input")
+    if part is None:
+        part = torch.empty((2, B, 16), dtype=torch.float32, device=h.device)
+    if tuple(part.shape) != (2, B, 16) or part.dtype != torch.float32 or not part.is_contiguous():
+        raise ValueError(f"head_forward: part must be contiguous fp32 (2,{B},16), got {part.dtype} {tuple(part.shape)}")
+    probs = probs if probs is not None else torch.empty((B, 10), dtype=torch.float32, device=h.device)
+    pred = pred if pred is not None else torch.empty((B,), dtype=torch.int32, device=h.device)
+    check(lib().cifar_fc1_head_x3(ptr(h), 4096, ptr(w.w_fc1h), ptr(w.w_fc1l), 4096, ptr(w.b_fc1), ptr(w.w_fc2h),
+                                  ptr(w.w_fc2l), ptr(w.b_fc2), ptr(part), ptr(probs), ptr(pred), B, 512, 4096,
+                                  stream_ptr(), split), "cifar_fc1_head_x3")
+    return probs, pred

@@ -120,7 +120,10 @@ class CifarHipStage(StageCompute):
         w, dt = self._boundary(self.end)
         return (batch, w), dt
 
-    def _buf(self, batch):
+    def _buf(self, batch, fused=False):
+        """Scratch for ``batch`` rows.  ``fused``: units 2-3 run as the fused fp32 head (decided once per
+        forward), which takes partial logits instead of the hidden rows; only the path that runs gets
+        its buffer, on first use, since the switch may change between calls."""
         b = self._scratch.get(batch)
         if b is None:
             d = self.device
@@ -130,14 +133,20 @@ class CifarHipStage(StageCompute):
             if self.start <= 2 <= self.end and self.precision == "fp32" and batch < self._cops.FC1_X3_MIN_ROWS:
                 b["split"] = torch.empty((batch, 3 * 4096), dtype=torch.bfloat16, device=d)
             if self.last:
-                b["hid"] = torch.empty((batch, 512), dtype=self.adt, device=d)
                 b["pred"] = torch.empty((batch,), dtype=torch.int32, device=d)
             self._scratch[batch] = b
+        if self.last and self.start <= 2:
+            if fused:
+                if "part" not in b:
+                    b["part"] = torch.empty((2, batch, 16), dtype=torch.float32, device=self.device)
+            elif "hid" not in b:
+                b["hid"] = torch.empty((batch, 512), dtype=self.adt, device=self.device)
         return b
 
     def forward(self, x, out=None):
         B = x.shape[0]
-        buf = self._buf(B)
+        fused = self.start <= 2 and self.end == 3 and self._cops._head_fused(self.wh, B)
+        buf = self._buf(B, fused)
         h = x
         if self.first:
             if self.input_dtype == "uint8":
@@ -151,11 +160,14 @@ class CifarHipStage(StageCompute):
                 return h
         elif h.dtype != self.adt:
             h = h.to(self.adt)
-        if self.start <= 2 <= self.end:
-            h = self._cops.fc1_forward(h.contiguous(), self.wh, out if self.end == 2 else buf["hid"],
-                                       scratch=buf.get("split"), boundary=self.boundary)
-            if self.end == 2:
-                return h
+        if self.start <= 2 and self.end == 3:
+            probs, pred = self._cops.head_forward(h.contiguous(), self.wh, buf.get("hid"), out, buf["pred"],
+                                                  boundary=self.boundary, part=buf.get("part"),
+                                                  scratch=buf.get("split"), fused=fused)
+            return StageOutput(probs, pred)
+        if self.end == 2:  # the fc1 cut: the hidden rows are the stage's output
+            return self._cops.fc1_forward(h.contiguous(), self.wh, out, scratch=buf.get("split"),
+                                          boundary=self.boundary)
         probs, pred = self._cops.head_tail(h.contiguous(), self.wh, out, buf["pred"])
         return StageOutput(probs, pred)
 

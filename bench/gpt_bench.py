@@ -45,8 +45,9 @@ def parse(argv=None):
     ap.add_argument("--prompt", type=int, default=512)
     ap.add_argument("--prefill_iters", type=int, default=5)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"])
-    ap.add_argument("--mxfp4-prefill", dest="mxfp4_prefill", default="bf16", choices=["bf16", "e4m3"],
-                    help="mxfp4 weights: prefill pieces above 64 rows expand to bf16 (default) or run W4A8 on the codes")
+    ap.add_argument("--mxfp4-prefill", dest="mxfp4_prefill", default="bf16", choices=["bf16", "e4m3", "w4a16"],
+                    help="mxfp4 weights: prefill pieces above 64 rows expand to bf16 (default), run W4A8 on the codes, "
+                         "or (w4a16) every expanding step runs the W4A16 tile GEMM on the codes")
     ap.add_argument("--mxfp4-head", dest="mxfp4_head", action="store_true",
                     help="mxfp4 weights: the vocabulary head as a folded MXFP4 weight too (mxfp4_head: \"mxfp4\")")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "fp8"], help="KV cache dtype (fp8: OCP e4m3)")

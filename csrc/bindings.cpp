@@ -81,6 +81,13 @@ PYBIND11_MODULE(_dnn_hip, m) {
   }, py::arg("A"), py::arg("lda"), py::arg("Wq"), py::arg("Ws"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
      py::arg("R"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("act"), py::arg("norm"),
      py::arg("colsum"), py::arg("eps"), py::arg("st"));
+  m.def("gemm_w4_tile", [](u64 A, int lda, u64 Wq, u64 Ws, u64 C, int ldc, u64 bias, u64 R, int ldr, int M, int N,
+                           int K, int act, int norm, u64 colsum, float eps, u64 st) {
+    return dnn_gemm_w4_tile(CP(A), lda, CP(Wq), CP(Ws), P(C), ldc, CFP(bias), CP(R), ldr, M, N, K, act, norm,
+                            CFP(colsum), eps, ST(st));
+  }, py::arg("A"), py::arg("lda"), py::arg("Wq"), py::arg("Ws"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
+     py::arg("R"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("act"), py::arg("norm"),
+     py::arg("colsum"), py::arg("eps"), py::arg("st"));
   m.def("gemm_w4_head", [](u64 A, int lda, u64 Wq, u64 Ws, u64 C, int ldc, u64 bias, int M, int N, int K, int norm,
                            u64 colsum, float eps, u64 part, int part_cap, u64 st) {
     return dnn_gemm_w4_head(CP(A), lda, CP(Wq), CP(Ws), P(C), ldc, CFP(bias), M, N, K, norm, CFP(colsum), eps,

@@ -232,6 +232,14 @@ int dnn_gemm_w4_mid(const void* A, int lda, const void* Wq, const void* Ws, void
 int dnn_gemm_w4_mn(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
                    const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
                    hipStream_t st);
+// dnn_gemm_w4_tile (gemm_w4_tile.h): the contract and returns of dnn_gemm_w4_mid for any M >= 1 (-2 only below 1;
+// -3 also for N above 65535 x 128): the compute-bound form, a grid of ceil(M / 128) x ceil(N / 128) workgroups
+// that each own a 128 x 128 output block over the whole of K (A through LDS, the codes converted in registers,
+// no K split, no atomics: the same bits on every launch).  R may be C.  What mxfp4_prefill "w4a16" runs where the
+// other modes expand the weight.
+int dnn_gemm_w4_tile(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc, const float* bias,
+                     const void* R, int ldr, int M, int N, int K, int act, int norm, const float* colsum, float eps,
+                     hipStream_t st);
 int dnn_w4_expand(const void* Wq, const void* Ws, void* W, int ldw, int N, int K, hipStream_t st);
 // dnn_gemm_w4_head (gemm_w4_head.h): the MXFP4 vocabulary head, 1 <= M <= 64: bf16 logits C = norm-folded
 // A . dq(W)^T + bias from persistent workgroups (at most one per CU, A in LDS), and with part != nullptr each

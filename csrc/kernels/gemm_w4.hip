@@ -54,6 +54,10 @@
 // out of the statistics).  A wave's short last batch clamps its surplus loads
 // to its last chunk and skips their math.
 //
+// Further kernels on the same weight, included below: gemm_w4_mid.h (65..256 rows, A through LDS), gemm_w4_mn.h
+// (65..256 rows on narrow projections), gemm_w4_tile.h (any number of rows, 128 x 128 blocks: the compute-bound
+// form, mxfp4_prefill "w4a16"), gemm_w4a8.h (prefill on MX e4m3 activations), gemm_w4_head.h (the vocabulary head).
+//
 // dnn_w4_expand.  One wave per (tile, chunk) block: it reads the block as the
 // GEMM does (1 KiB of codes, 64 scale bytes), converts its 32 codes to 64 B of
 // bf16 and transposes through LDS (row pitch 272 B, so the 16 rows of a lane
@@ -252,6 +256,7 @@ __global__ __launch_bounds__(512) void gemm_w4_kernel(const uint8_t* __restrict_
 
 #include "gemm_w4_mid.h"  // dnn_gemm_w4_mid's kernel: up to 256 rows, A shared through LDS
 #include "gemm_w4_mn.h"   // dnn_gemm_w4_mn's kernel: up to 256 rows on narrow projections, an M x N grid, waves split K
+#include "gemm_w4_tile.h"  // dnn_gemm_w4_tile's kernel: any number of rows, 128 x 128 blocks over the whole of K, compute-bound
 #include "gemm_w4a8.h"    // dnn_gemm_w4a8: prefill on MX e4m3 activations, the codes on the scaled MFMA
 #include "gemm_w4_head.h"  // dnn_gemm_w4_head: the vocabulary head, persistent workgroups, argmax partials
 
@@ -436,6 +441,48 @@ extern "C" int dnn_gemm_w4_mn(const void* A, int lda, const void* Wq, const void
     case ACT_RELU: return launch_w4_mn<ACT_RELU>(norm, W4_ARGS);
     case ACT_GELU: return launch_w4_mn<ACT_GELU>(norm, W4_ARGS);
     default: return launch_w4_mn<ACT_SILU_MUL>(norm, W4_ARGS);
+  }
+#undef W4_ARGS
+}
+
+// dnn_gemm_w4_tile: one workgroup per 128 rows x 128 columns over the whole of K, the row blocks in grid x so that
+// the workgroups of a column block are dispatched together (gemm_w4_tile.h).
+template <int ACT>
+static int launch_w4_tile(int norm, const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc,
+                          const float* bias, const void* R, int ldr, int M, int N, int K, const float* colsum,
+                          float eps, hipStream_t st) {
+  const dim3 grid((M + W4T_BM - 1) / W4T_BM, (N + W4T_BN - 1) / W4T_BN);
+#define W4T_LAUNCH(NORM)                                                                                           \
+  hipLaunchKernelGGL((gemm_w4_tile_kernel<ACT, NORM>), grid, dim3(256), W4T_LDS, st, (const uint8_t*)A, lda * 2, \
+                     (const uint8_t*)Wq, (const uint8_t*)Ws, (bf16_t*)C, ldc, bias, (const bf16_t*)R, ldr, M, N, K, \
+                     colsum, eps)
+  switch (norm) {
+    case W4_NORM_NONE: W4T_LAUNCH(W4_NORM_NONE); break;
+    case W4_NORM_RMS: W4T_LAUNCH(W4_NORM_RMS); break;
+    default: W4T_LAUNCH(W4_NORM_LN); break;
+  }
+#undef W4T_LAUNCH
+  return (int)hipGetLastError();
+}
+
+extern "C" int dnn_gemm_w4_tile(const void* A, int lda, const void* Wq, const void* Ws, void* C, int ldc,
+                                const float* bias, const void* R, int ldr, int M, int N, int K, int act, int norm,
+                                const float* colsum, float eps, hipStream_t st) {
+  if (A == nullptr || Wq == nullptr || Ws == nullptr || C == nullptr) return -1;
+  if (norm == W4_NORM_LN && colsum == nullptr) return -1;
+  if (M < 1) return -2;
+  if (N < 1 || K < 32 || K % 32 != 0 || act < ACT_NONE || act > ACT_SILU_MUL || norm < 0 || norm > W4_NORM_LN ||
+      (act == ACT_SILU_MUL && N % 16 != 0) || (N + W4T_BN - 1) / W4T_BN > 65535)
+    return -3;
+  const int NO = act == ACT_SILU_MUL ? N / 2 : N;
+  if (ldc < NO || lda < K || (R != nullptr && ldr < NO)) return -4;
+  if ((((uintptr_t)A | (uintptr_t)Wq) & 15) != 0 || (lda & 7) != 0) return -5;
+#define W4_ARGS A, lda, Wq, Ws, C, ldc, bias, R, ldr, M, N, K, colsum, eps, st
+  switch (act) {
+    case ACT_NONE: return launch_w4_tile<ACT_NONE>(norm, W4_ARGS);
+    case ACT_RELU: return launch_w4_tile<ACT_RELU>(norm, W4_ARGS);
+    case ACT_GELU: return launch_w4_tile<ACT_GELU>(norm, W4_ARGS);
+    default: return launch_w4_tile<ACT_SILU_MUL>(norm, W4_ARGS);
   }
 #undef W4_ARGS
 }

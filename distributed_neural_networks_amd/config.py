@@ -269,7 +269,7 @@ class PipelineConfig:
     kv_cache_dtype: str = "bf16"              # "fp8": OCP e4m3 KV cache (half the decode K/V bytes)
     kv_cache_scale: str = "calibrated"        # fp8 cache: per-layer scale from the first prefill's amax, or "unit"
     fp8_prefill: str = "e4m3"                 # dtype fp8: prefill activations "e4m3" (one byte, per-row scale) or "split" (e4m3 hi + residual)
-    mxfp4_prefill: str = "bf16"               # dtype mxfp4: prefill above 64 rows "bf16" (expand + bf16 GEMM) or "e4m3" (W4A8 on the codes)
+    mxfp4_prefill: str = "bf16"               # dtype mxfp4: prefill above 64 rows "bf16" (expand + bf16 GEMM), "e4m3" (W4A8 on the codes) or "w4a16" (bf16 activations on the codes wherever "bf16" expands, decode above 256 rows too)
     mxfp4_head: str = "bf16"                  # dtype mxfp4: the vocabulary head "bf16" or "mxfp4" (folded MXFP4 weight, ops/w4.py head_w4)
     transport: str = "grpc"
     micro_batch_size: int = 1
@@ -425,8 +425,8 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
     if fpp not in ("split", "e4m3"):
         raise ConfigError(f"ERROR: 'fp8_prefill' must be 'split' or 'e4m3', got {fpp!r}")
     m4p = cfg.get("mxfp4_prefill", "bf16")
-    if m4p not in ("bf16", "e4m3"):
-        raise ConfigError(f"ERROR: 'mxfp4_prefill' must be 'bf16' or 'e4m3', got {m4p!r}")
+    if m4p not in ("bf16", "e4m3", "w4a16"):
+        raise ConfigError(f"ERROR: 'mxfp4_prefill' must be 'bf16', 'e4m3' or 'w4a16', got {m4p!r}")
     if m4p != "bf16" and cfg.get("dtype") != "mxfp4":
         raise ConfigError(f"ERROR: 'mxfp4_prefill' {m4p!r} needs dtype 'mxfp4', got {cfg.get('dtype')!r}")
     m4h = cfg.get("mxfp4_head", "bf16")

@@ -266,11 +266,12 @@ def linear_norm(x: torch.Tensor, f: FoldedLinear, act=None, residual: Optional[t
                 s8: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
                 rs_in: Optional[torch.Tensor] = None, sx: Optional[torch.Tensor] = None,
                 q_out: Optional[tuple] = None, scratch: Optional[torch.Tensor] = None,
-                mn: bool = False) -> torch.Tensor:
+                mn: bool = False, tile: bool = False) -> torch.Tensor:
     """``linear(norm(x), W, b)`` for a ``FoldedLinear``.  An MXFP4 weight
     (``fold_norm(quant="mxfp4")``) goes to ``w4.linear_w4`` (``scratch``: its
     bf16 expand buffer; without one 65..256 rows run ``dnn_gemm_w4_mid``, or
-    with ``mn`` ``dnn_gemm_w4_mn``), or, with ``q8`` and
+    with ``mn`` ``dnn_gemm_w4_mn``; with ``tile`` more than 64 rows run
+    ``dnn_gemm_w4_tile``, whatever their number), or, with ``q8`` and
     ``sx`` given, to ``layernorm_q8_mx`` + ``w4.linear_w4a8`` (MX e4m3 activations).  ``rs_in`` (decode):
     the row-statistics partials of ``x`` written by its producer (``linear(...,
     rs_out=)``), merged instead of deriving the statistics from ``x``.  Decode-sized M (<= 64):
@@ -294,7 +295,7 @@ def linear_norm(x: torch.Tensor, f: FoldedLinear, act=None, residual: Optional[t
             layernorm_q8_mx(x, ones, None, q8, sx, f.w.kpad, f.eps, f.norm == NORM_RMS, rows=M, ldx=x.stride(0))
             return linear_w4a8(x, f.w, f.bias, a, residual, out, q8, sx, prequantized=True)
         return linear_w4(x, f.w, f.bias, a, residual, out, f.norm, f.colsum, f.eps, scratch=scratch, std_buf=std_buf,
-                         ones=ones, mn=mn)
+                         ones=ones, mn=mn, tile=tile)
     M, K = x.shape
     w8 = isinstance(f.w, Fp8Weight)
     N = f.w.shape[0]

@@ -26,7 +26,11 @@ Projections too narrow for its N / 64 workgroups run ``dnn_gemm_w4_mn``
 With a caller-supplied bf16 scratch, more than 64 rows expand the weight
 (``dnn_w4_expand``) and run the bf16 tile kernels on it, with their
 folded-norm, QKV-scatter, GELU, SwiGLU and residual epilogues unchanged: the
-prefill route, and the only one above 256 rows.
+prefill route, and without ``tile`` the only one above 256 rows.
+``linear_w4(tile=True)`` runs any M > 64 as one ``dnn_gemm_w4_tile`` launch
+instead (``csrc/kernels/gemm_w4_tile.h``: 128 x 128 output blocks over the
+whole of K, A through LDS, the codes converted in registers; no scratch, no row
+limit): what ``mxfp4_prefill: "w4a16"`` runs wherever the other modes expand.
 
 A vocabulary head (``fold_norm(quant="mxfp4")`` of ``lm_head``) at up to 64 rows
 runs ``head_w4`` (``dnn_gemm_w4_head``, ``csrc/kernels/gemm_w4_head.h``):
@@ -256,7 +260,7 @@ def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = No
               residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, norm: int = 0,
               colsum: Optional[torch.Tensor] = None, eps: float = 0.0, scratch: Optional[torch.Tensor] = None,
               std_buf: Optional[torch.Tensor] = None, ones: Optional[torch.Tensor] = None,
-              mn: bool = False) -> torch.Tensor:
+              mn: bool = False, tile: bool = False) -> torch.Tensor:
     """bf16 x (M, K) times an MXFP4 weight, bf16 out.  ``norm`` (1 RMS / 2 LN,
     with ``colsum`` for LN) is a folded pre-norm (``gemm.fold_norm(quant="mxfp4")``).
     M <= 64: one ``dnn_gemm_w4`` launch.  M > 64 with ``scratch`` (bf16, >= N K
@@ -264,14 +268,16 @@ def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = No
     ``gemm.linear_norm`` run on it (``std_buf`` / ``ones`` as ``linear_norm``).
     65 <= M <= 256 without a scratch: one ``dnn_gemm_w4_mid`` launch on the
     codes, or with ``mn`` one ``dnn_gemm_w4_mn`` launch (the M x N grid for
-    narrow projections, ``w4_mn_ok``).  More than 256 rows need the scratch."""
+    narrow projections, ``w4_mn_ok``).  More than 256 rows need the scratch,
+    unless ``tile``: then M > 64 is one ``dnn_gemm_w4_tile`` launch on the codes
+    (any M, no scratch; ``mn`` and ``scratch`` are not used)."""
     M, K = x.shape
     N = w.n
     if K != w.k:
         raise ValueError(f"linear_w4: x {tuple(x.shape)} vs weight {w.shape}")
     if x.dtype != torch.bfloat16 or x.stride(1) != 1:
         raise TypeError("linear_w4: bf16 activations with a contiguous last dim")
-    if M > W4_MAX_M and (scratch is not None or M > W4_MID_MAX_M):
+    if M > W4_MAX_M and not tile and (scratch is not None or M > W4_MID_MAX_M):
         from .gemm import FoldedLinear, linear, linear_norm
         if scratch is None:
             raise ValueError("linear_w4: more than 256 rows need the bf16 expand scratch")
@@ -290,6 +296,8 @@ def linear_w4(x: torch.Tensor, w: Mxfp4Weight, bias: Optional[torch.Tensor] = No
         raise ValueError("linear_w4: bad residual")
     if M <= W4_MAX_M:
         fn, name = lib().gemm_w4, "gemm_w4"
+    elif tile:
+        fn, name = lib().gemm_w4_tile, "gemm_w4_tile"
     elif mn:
         fn, name = lib().gemm_w4_mn, "gemm_w4_mn"
     else:

@@ -30,7 +30,9 @@ run the W4A16 decode kernel, so a decode graph holds no other projection
 kernel; steps of more rows (prefill, chunked prefill, decode microbatches
 above 64 rows) expand each projection into the stage's one bf16 scratch and
 run the bf16 kernels on it — a decode microbatch above 64 rows therefore pays
-one expansion per projection per step.
+one expansion per projection per step.  ``mxfp4_prefill="w4a16"`` runs every such
+step on the codes instead (``dnn_gemm_w4_tile``, csrc/kernels/gemm_w4_tile.h: any
+number of rows, bf16 activations); that mode allocates no expand scratch.
 All positions/lengths live in device memory so a decode step is one graph.
 """
 from __future__ import annotations
@@ -103,12 +105,15 @@ class TransformerStage(StageCompute):
         self.w4 = bool(w4)
         # MXFP4 weights, prefill pieces of more than 64 rows: "bf16" (default) = expand each projection to
         # bf16 and run the bf16 tile kernels; "e4m3" = MX e4m3 activations against the codes on the scaled
-        # MFMA (ops/w4.py linear_w4a8: no expansion, the fp8 MFMA rate)
-        if mxfp4_prefill not in ("bf16", "e4m3"):
-            raise ValueError(f"mxfp4_prefill {mxfp4_prefill!r}: bf16 or e4m3")
+        # MFMA (ops/w4.py linear_w4a8: no expansion, the fp8 MFMA rate); "w4a16" = bf16 activations against
+        # the codes (dnn_gemm_w4_tile) on every step that "bf16" expands, decode above 256 rows and the MXFP4
+        # head's all-position logits included: no expand scratch
+        if mxfp4_prefill not in ("bf16", "e4m3", "w4a16"):
+            raise ValueError(f"mxfp4_prefill {mxfp4_prefill!r}: bf16, e4m3 or w4a16")
         if mxfp4_prefill != "bf16" and not w4:
-            raise ValueError("mxfp4_prefill 'e4m3' needs MXFP4 weights (dtype mxfp4)")
+            raise ValueError(f"mxfp4_prefill {mxfp4_prefill!r} needs MXFP4 weights (dtype mxfp4)")
         self.mxfp4_prefill = mxfp4_prefill
+        self.w4_tile = bool(w4) and mxfp4_prefill == "w4a16"  # the tile kernel wherever "bf16" expands
         # MXFP4 weights, the vocabulary head: "bf16" (default) = the bf16 folded head; "mxfp4" = the last
         # stage holds ln_f + lm_head only as a folded MXFP4 weight (ops/w4.py head_w4 at up to 64 rows)
         if mxfp4_head not in ("bf16", "mxfp4"):
@@ -195,11 +200,11 @@ class TransformerStage(StageCompute):
         self.ones = torch.ones((self.d,), dtype=torch.float32, device=dev)
         self.layers: List[LayerW] = [self._pack_layer(sd, j) for j in range(end - start + 1)]
         # MXFP4: the one bf16 expand scratch of the steps above 64 rows, sized to the largest projection
-        # (allocated here, never inside a graph capture)
+        # (allocated here, never inside a graph capture); none with mxfp4_prefill "w4a16", which expands nothing
         self.w4_scratch = None
         self._w4_decode = False  # the running step is a decode step (T == 1): set by ``step``
         self._w4_a8 = False      # the running step is a W4A8 prefill piece (mxfp4_prefill "e4m3"): set by ``step``
-        if self.w4:
+        if self.w4 and not self.w4_tile:
             big = max(w.n * w.k for L in self.layers
                       for w in (L.w_qkv.w, L.w_o, L.w_up.w, L.w_down))
             if self.head_w4:  # all-position logits of more than 256 rows expand the head too
@@ -675,7 +680,7 @@ class TransformerStage(StageCompute):
             if self._w4_a8:  # W4A8 prefill piece: quantise pass + the codes on the scaled MFMA
                 return linear_w4a8(x, w, b, act, residual, out, self.q8, self.sx8), False
             return linear_w4(x, w, b, act, residual, out, scratch=self._w4_scratch_for(x.shape[0], w),
-                             mn=self._w4_mn(x.shape[0], w)), False
+                             mn=self._w4_mn(x.shape[0], w), tile=self._w4_tile(x.shape[0], w)), False
         if self.fp8:
             from ..ops.fp8 import linear_fp8, linear_w8
             if skinny_rows(x.shape[0], w.q.shape[0], w8=True):  # decode: weight-only fp8 (bf16 activations)
@@ -687,16 +692,25 @@ class TransformerStage(StageCompute):
         y = linear(x, w, b, act, residual, out, w_shuf=w_shuf, ws=ws, rs_out=rs_out)
         return y, rs_out is not None and rowstats_written()
 
+    def _w4_wide(self, rows: int, w) -> bool:
+        """Whether this step is outside the decode-sized W4A16 kernels on the
+        MXFP4 weight ``w``: prefill pieces of more than 64 rows, steps above
+        256 rows, and the decode shapes neither ``w4_mid_ok`` nor ``w4_mn_ok``
+        takes (W4A8 pieces excluded)."""
+        from ..ops.w4 import W4_MAX_M, w4_mid_ok, w4_mn_ok
+        return not (rows <= W4_MAX_M or self._w4_a8 or (self._w4_decode and (w4_mid_ok(rows, w.n, w.k) or
+                                                                             w4_mn_ok(rows, w.n, w.k))))
+
     def _w4_scratch_for(self, rows: int, w):
         """The expand scratch where this step expands the MXFP4 weight ``w``
-        (prefill pieces of more than 64 rows, steps above 256 rows, and the
-        decode shapes neither ``w4_mid_ok`` nor ``w4_mn_ok`` takes), else None:
-        the W4A16 kernels run on the codes."""
-        from ..ops.w4 import W4_MAX_M, w4_mid_ok, w4_mn_ok
-        if rows <= W4_MAX_M or self._w4_a8 or (self._w4_decode and (w4_mid_ok(rows, w.n, w.k) or
-                                                                    w4_mn_ok(rows, w.n, w.k))):
-            return None
-        return self.w4_scratch
+        (``_w4_wide``, unless ``mxfp4_prefill`` is "w4a16"), else None: the
+        W4A16 kernels run on the codes."""
+        return self.w4_scratch if self._w4_wide(rows, w) and not self.w4_tile else None
+
+    def _w4_tile(self, rows: int, w) -> bool:
+        """``mxfp4_prefill`` "w4a16", a step the other modes expand
+        (``_w4_wide``): ``linear_w4`` runs ``dnn_gemm_w4_tile`` on the codes."""
+        return bool(self.w4_tile and self._w4_wide(rows, w))
 
     def _w4_mn(self, rows: int, w) -> bool:
         """MXFP4 stage, a decode step of 65..256 rows on a projection of
@@ -799,7 +813,9 @@ class TransformerStage(StageCompute):
             kc, vc = self.kc[li, b0:b0 + B], self.vc[li, b0:b0 + B]
             att = self.buf_att[r0:r1]
             w_qkv = self._w4x(L.w_qkv, ntok)
-            scattered = (not a8 and T > 1 and self.cos is None and self.fuse_norm and
+            # (mxfp4_prefill "w4a16", like "e4m3": c_attn writes buf_qkv and flash_attn_qkv reads it)
+            scattered = (not a8 and not self._w4_tile(ntok, L.w_qkv.w) and T > 1 and self.cos is None and
+                         self.fuse_norm and
                          qkv_scatter_norm(h_in, w_qkv, a, self.buf_q, kc, vc, pos, B, T, self.H, self.Hkv,
                                           self.hd, ones=self.ones, q8=q8, s8=s8, sx=self.sx8 if T > 1 else None))
             if scattered:
@@ -807,7 +823,7 @@ class TransformerStage(StageCompute):
             elif self.fuse_norm:
                 qkv = linear_norm(h_in, w_qkv, out=self.buf_qkv[r0:r1], std_buf=a, ones=self.ones, q8=q8,
                                   s8=s8, ws=gws, rs_in=rs if have_rs else None, sx=self.sx8 if a8 else None,
-                                  mn=self._w4_mn(ntok, L.w_qkv.w))
+                                  mn=self._w4_mn(ntok, L.w_qkv.w), tile=self._w4_tile(ntok, L.w_qkv.w))
             else:
                 T_.layernorm(h_in, L.ln1_w, L.ln1_b, a, self.eps, self.rms, rows=ntok)
                 qkv, _ = self._lin(a, L.w_qkv, L.b_qkv, out=self.buf_qkv[r0:r1])
@@ -831,7 +847,8 @@ class TransformerStage(StageCompute):
                     mx_f = (self.q8b, self.sx8b)
                 f = linear_norm(h, self._w4x(L.w_up, ntok), act=up_act, out=self.buf_f[r0:r1], std_buf=a, ones=self.ones, q8=q8,
                                 s8=s8, ws=gws, rs_in=rs if have_rs else None,
-                                sx=self.sx8 if T > 1 else None, q_out=mx_f, mn=self._w4_mn(ntok, L.w_up.w))
+                                sx=self.sx8 if T > 1 else None, q_out=mx_f, mn=self._w4_mn(ntok, L.w_up.w),
+                                tile=self._w4_tile(ntok, L.w_up.w))
                 if mx_f is not None:
                     f = self.buf_f[r0:r1]  # shape only: c_proj reads the e4m3 bytes in mx_f
             else:
@@ -928,9 +945,11 @@ class TransformerStage(StageCompute):
             x_last = torch.as_strided(src, (rows, d), (ldx, 1))
             if self.head_w4 and rows <= W4_MAX_M:
                 head_w4(x_last, self.w_head, logits[:, :self.V])  # the logits only
-            elif self.head_w4:  # 65..256 rows: dnn_gemm_w4_mid on the codes; more: expand + the bf16 linear_norm
+            elif self.head_w4:  # 65..256 rows: dnn_gemm_w4_mid on the codes; more: expand + the bf16 linear_norm,
+                # or with mxfp4_prefill "w4a16" dnn_gemm_w4_tile on the codes
                 linear_norm(x_last, self.w_head, out=logits[:, :self.V], std_buf=self.buf_lnf[r0:], ones=self.ones,
-                            scratch=self.w4_scratch if rows > W4_MID_MAX_M else None)
+                            scratch=self.w4_scratch if rows > W4_MID_MAX_M else None,
+                            tile=self.w4_tile and rows > W4_MID_MAX_M)
             else:
                 linear_norm(x_last, self.w_head, out=logits[:, :self.V], std_buf=self.buf_lnf[r0:], ones=self.ones,
                             q8=q8, s8=s8, ws=gws)

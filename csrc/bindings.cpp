@@ -309,6 +309,22 @@ PYBIND11_MODULE(_dnn_hip, m) {
   }, py::arg("x"), py::arg("ld"), py::arg("M"), py::arg("N"), py::arg("tok"), py::arg("pos"), py::arg("pos_off"),
      py::arg("n"), py::arg("lp_hist"), py::arg("top_id_hist"), py::arg("top_lp_hist"), py::arg("hist_ld"),
      py::arg("top_ld"), py::arg("ws"), py::arg("ws_rows"), py::arg("ws_ld"), py::arg("st"));
+  m.def("head_lse_slices", [](int M, int V) { return dnn_head_lse_slices(M, V); });
+  // both launches of head_lse.hip: the partials, then the merge that scatters into the histories
+  m.def("head_lse", [](u64 A, int lda, u64 W, int ldw, u64 rowstat, u64 colsum, u64 bias, u64 target, u64 out_idx,
+                       int M, int V, int d, u64 ws, long long ws_bytes, u64 tok_lp, u64 top_id, u64 top_lp,
+                       long long out_len, u64 st) {
+    // the merge's operands are checked before the first launch: a rejected call launches nothing
+    if (out_idx == 0 || tok_lp == 0 || top_id == 0 || top_lp == 0 || out_len < 1 || ((out_idx | tok_lp | top_id | top_lp) & 3))
+      return -1;
+    const int rc = dnn_head_lse(CP(A), lda, CP(W), ldw, CFP(rowstat), CFP(colsum), CFP(bias), CIP(target), M, V, d,
+                                P(ws), ws_bytes, ST(st));
+    if (rc != 0) return rc;
+    return dnn_head_lse_finish(CP(ws), ws_bytes, CIP(target), CIP(out_idx), M, V, FP(tok_lp), IP(top_id), FP(top_lp),
+                               out_len, ST(st));
+  }, py::arg("A"), py::arg("lda"), py::arg("W"), py::arg("ldw"), py::arg("rowstat"), py::arg("colsum"),
+     py::arg("bias"), py::arg("target"), py::arg("out_idx"), py::arg("M"), py::arg("V"), py::arg("d"), py::arg("ws"),
+     py::arg("ws_bytes"), py::arg("tok_lp"), py::arg("top_id"), py::arg("top_lp"), py::arg("out_len"), py::arg("st"));
   m.attr("STOP_STATE_WORDS") = DNN_STOP_STATE_WORDS;
   m.def("stop_rows", [](u64 tok, u64 also, u64 hist, int hist_ld, u64 pos, int pos_off, u64 state,
                         const std::vector<int>& stop_ids, const std::vector<std::vector<int>>& stop_seqs, int min_new,

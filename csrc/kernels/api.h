@@ -161,6 +161,21 @@ int dnn_logprobs_ws_row_words(int N, int n);
 int dnn_logprobs_rows(const void* x, int ld, int M, int N, const int* tok, const int* pos, int pos_off, int n,
                       float* lp_hist, int* top_id_hist, float* top_lp_hist, int hist_ld, int top_ld, void* ws,
                       int ws_rows, int ws_ld, hipStream_t st);
+// prompt log-probabilities without a logits tensor (head_lse.hip, which states the math and the split): the
+// head GEMM A (M, d) . W (V, d)^T, both bf16 row-major, folded by rowstat ({rstd, -mean rstd} per row from
+// dnn_row_stats, or null), colsum and bias (fp32 (V), or null), rounded to bf16 and reduced per row in the
+// epilogue.  dnn_head_lse leaves dnn_head_lse_slices(M, V) partials of 16 bytes per row in ws;
+// dnn_head_lse_finish merges them and writes tok_lp / top_id / top_lp at index out_idx[row] of buffers of out_len
+// entries (rows whose target is outside [0, V) or whose index is outside [0, out_len) write nothing).
+// -1, nothing launched: a null A / W / target / ws / out_idx / output, M < 1, V < 1, d not a positive multiple
+// of 64, lda or ldw below d or not a multiple of 8, colsum without rowstat, A / W / ws / colsum / bias not 16-byte
+// aligned, ws_bytes below 16 M slices.
+int dnn_head_lse_slices(int M, int V);
+int dnn_head_lse(const void* A, int lda, const void* W, int ldw, const float* rowstat, const float* colsum,
+                 const float* bias, const int* target, int M, int V, int d, void* ws, long long ws_bytes,
+                 hipStream_t st);
+int dnn_head_lse_finish(const void* ws, long long ws_bytes, const int* target, const int* out_idx, int M, int V,
+                        float* tok_lp, int* top_id, float* top_lp, long long out_len, hipStream_t st);
 // stop tokens / stop sequences / min_new_tokens (stop.hip, which states the semantics).  state: int32
 // [rows][DNN_STOP_STATE_WORDS] on the device = {g, finish length (0 = running), reason code (1 + id index,
 // 17 + sequence index), the last 15 generated tokens newest first}.  The tables are HOST arrays, copied into

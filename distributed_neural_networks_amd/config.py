@@ -13,7 +13,7 @@ Behavioural contract (reference ``node.py:222-290``, ``config.json:1-18``):
   top level ``model``, ``dtype``, ``transport``, ``micro_batch_size``,
   ``num_microbatches``, ``seq_len``, ``decode_steps``, ``prompt_len``, ``prompts``, ``temperature``, ``top_k``,
   ``top_p``, ``min_p``, ``seed``, ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``,
-  ``logprobs``, ``eos_token_id``, ``stop_token_ids``, ``stop_sequences``, ``min_new_tokens``,
+  ``logprobs``, ``prompt_logprobs``, ``eos_token_id``, ``stop_token_ids``, ``stop_sequences``, ``min_new_tokens``,
   ``pad_token_id``, ``logit_bias``, ``allowed_token_ids``, ``bad_words_ids``, ``no_repeat_ngram_size``,
   ``heartbeat_timeout_s``, ``stall_timeout_s``, ``prefill_chunk``, ``replicas``,
   ``kv_cache_dtype``, ``kv_cache_scale``, ``fp8_prefill``, ``mxfp4_prefill``, ``mxfp4_head``, ``input_dtype``, ``input_mean``,
@@ -288,6 +288,7 @@ class PipelineConfig:
     presence_penalty: float = 0.0             # subtracted once from the logit of every generated token (0 = off)
     frequency_penalty: float = 0.0            # subtracted per time the token was generated (0 = off)
     logprobs: int = 0                         # 1..20: record each token's log-probability and the top-n (0 = off)
+    prompt_logprobs: int = 0                  # 1: every prompt token's log-probability and the most likely entry
     stop: Optional[StopConfig] = None         # stop ids / sequences, min_new_tokens, pad_token_id (None = never stops)
     constraints: Optional[ConstraintConfig] = None  # logit_bias, allowed / bad ids, no_repeat_ngram_size (None = off)
     rpc_timeout_s: Optional[float] = None     # per-hop SendTensor deadline (reference: none)
@@ -460,6 +461,21 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         raise ConfigError(f"ERROR: 'logprobs' must be an integer in [0, {LOGPROBS_MAX_N}], got {nlp!r}")
     if model == "cifar10" and nlp != 0:
         raise ConfigError(f"ERROR: 'logprobs' {nlp!r} exists for the generating models only, got model '{model}'")
+    plp = cfg.get("prompt_logprobs", 0)
+    if not isinstance(plp, int) or isinstance(plp, bool) or plp < 0:
+        raise ConfigError(f"ERROR: 'prompt_logprobs' must be 0 or 1, got {plp!r}")
+    if plp > 1:
+        raise ConfigError(f"ERROR: 'prompt_logprobs' {plp!r}: only 1 exists (the prompt token's log-probability and the "
+                          f"single most likely entry); top-n alternatives on prompt positions are not recorded")
+    if plp:
+        if model == "cifar10":
+            raise ConfigError(f"ERROR: 'prompt_logprobs' exists for the generating models only, got model '{model}'")
+        if transport == "grpc":
+            raise ConfigError("ERROR: 'prompt_logprobs' needs an in-process or collective transport, not 'grpc'")
+        if cfg.get("dtype") == "fp8":
+            raise ConfigError("ERROR: 'prompt_logprobs' reads a bf16 vocabulary head: not with dtype 'fp8'")
+        if m4h == "mxfp4":
+            raise ConfigError("ERROR: 'prompt_logprobs' reads a bf16 vocabulary head: not with mxfp4_head 'mxfp4'")
     stop = None
     if any(cfg.get(k) is not None for k in STOP_KEYS):
         if model == "cifar10":
@@ -518,7 +534,7 @@ def parse_pipeline(cfg: Dict[str, Any], path: str = "<config>") -> PipelineConfi
         prefill_chunk=int(cfg.get("prefill_chunk", 0)),
         temperature=float(cfg.get("temperature", 0.0)), top_k=int(cfg.get("top_k", 0)), seed=int(cfg.get("seed", 0)),
         top_p=float(tp), min_p=float(mp), repetition_penalty=float(rp), presence_penalty=pens["presence_penalty"],
-        frequency_penalty=pens["frequency_penalty"], logprobs=nlp, stop=stop, constraints=cons,
+        frequency_penalty=pens["frequency_penalty"], logprobs=nlp, prompt_logprobs=plp, stop=stop, constraints=cons,
         rpc_timeout_s=cfg.get("rpc_timeout_s"), health_timeout_s=float(cfg.get("health_timeout_s", 120.0)),
         comm_timeout_s=float(cfg.get("comm_timeout_s", 300.0)),
         heartbeat_timeout_s=float(cfg.get("heartbeat_timeout_s", 15.0)),

@@ -49,6 +49,9 @@ PER_FILE_FLAGS = {"cifar_fused.hip": ["-ffast-math"],
                   "logprobs.hip": ["-ffp-contract=off"] + NO_SLP,
                   # logit_bias is one fp32 add rounded to bf16, bitwise its torch mirror
                   "constraints.hip": ["-ffp-contract=off"] + NO_SLP,
+                  # the fold's one fused multiply-add is written out (the unfused head's operations) and
+                  # (l - max) - lse stays two subtractions; scalar fp32 sums of exponentials
+                  "head_lse.hip": ["-ffp-contract=off"] + NO_SLP,
                   "gemm_skinny.hip": NO_SLP,
                   # scalar fp32 row statistics, as gemm_skinny.hip; and no packed fp32 VALU ops
                   # at all in this file (its GELU pairs compile to the scalar forms)

@@ -468,6 +468,75 @@ def head_argmax(x: torch.Tensor, f: FoldedLinear, logits: torch.Tensor, part: to
     return True
 
 
+def head_lse_workspace(M: int, V: int, device) -> torch.Tensor:
+    """Workspace of ``head_lse`` for ``M`` rows of a vocabulary of ``V``: one
+    16-byte partial per row and vocabulary slice (head_lse.hip; the number of
+    slices depends on ``(M, V)`` alone).  Every call writes the partials it
+    reads, so the buffer needs no clearing and calls may share it."""
+    ns = lib().head_lse_slices(int(M), int(V))
+    if ns < 1:
+        raise ValueError(f"head_lse_workspace: M = {M}, V = {V}")
+    return torch.empty((int(M), ns, 4), dtype=torch.float32, device=device)
+
+
+def head_lse(x: torch.Tensor, f, target: torch.Tensor, out_idx: torch.Tensor, tok_lp: torch.Tensor,
+             top_id: torch.Tensor, top_lp: torch.Tensor, ws: torch.Tensor, stats: Optional[torch.Tensor] = None,
+             rowstat: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> None:
+    """Log-probability of ``target[row]`` and the most likely entry of every
+    row's next-token distribution, without the logits (head_lse.hip): the head
+    GEMM of the bf16 rows ``x`` (M, d) against ``f`` (a ``FoldedLinear`` with a
+    bf16 weight, or a plain bf16 (V, d) weight with its ``bias``) with the log-sum-exp, the
+    argmax and the target's logit taken in its epilogue on the bf16-rounded
+    logits, the values ``linear_norm`` would store.  Row ``m`` writes
+    ``tok_lp / top_id / top_lp`` (flat views of the caller's histories) at
+    index ``out_idx[m]``; a row whose target is -1 (or outside the vocabulary)
+    writes nothing.  A folded norm takes its row statistics from ``row_stats``
+    into ``stats`` (fp32, >= 2 M entries), or ready-made from ``rowstat``
+    ((M, 2) fp32 {rstd, -mean rstd}).  ``ws``: ``head_lse_workspace(M, V)`` or
+    larger.  A shape the kernel does not cover is an error, never another route."""
+    folded = isinstance(f, FoldedLinear)
+    w = f.w if folded else f
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.bfloat16 or w.dim() != 2 or w.stride(1) != 1:
+        raise TypeError("head_lse: the head weight must be bf16 (V, d) with contiguous rows")
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"head_lse: x {tuple(x.shape)} {x.dtype} vs w {tuple(w.shape)}")
+    M, d = x.shape
+    V = w.shape[0]
+    if d % 64:
+        raise ValueError(f"head_lse: d = {d} must be a multiple of 64")
+    for t, nm in ((target, "target"), (out_idx, "out_idx")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < M:
+            raise ValueError(f"head_lse: {nm} must be contiguous int32 with >= {M} entries")
+    for t, nm, dt in ((tok_lp, "tok_lp", torch.float32), (top_id, "top_id", torch.int32),
+                      (top_lp, "top_lp", torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != tok_lp.numel() or t.numel() < 1:
+            raise ValueError(f"head_lse: {nm} must be contiguous {dt} with the size of tok_lp")
+    need = M * lib().head_lse_slices(M, V) * 16
+    if ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() * 4 < need:
+        raise ValueError(f"head_lse: workspace of {ws.numel() * 4} bytes, contiguous fp32 of >= {need} bytes expected")
+    colsum = None
+    if folded:
+        if bias is not None:
+            raise ValueError("head_lse: a FoldedLinear carries its own bias")
+        colsum, bias = f.colsum, f.bias
+        if rowstat is None:
+            if stats is None or stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() < 2 * M:
+                raise ValueError(f"head_lse: stats must be contiguous fp32 with >= {2 * M} entries")
+            from .transformer_ops import row_stats
+            rowstat = stats.view(-1)[:2 * M].view(M, 2)
+            row_stats(x, rowstat, f.eps, f.norm == NORM_RMS, rows=M, ldx=x.stride(0))
+    if rowstat is not None and (rowstat.dtype != torch.float32 or not rowstat.is_contiguous()
+                                or tuple(rowstat.shape) != (M, 2)):
+        raise ValueError(f"head_lse: rowstat must be contiguous fp32 ({M}, 2)")
+    for t, nm in ((colsum, "colsum"), (bias, "bias")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != V):
+            raise ValueError(f"head_lse: {nm} must be contiguous fp32 ({V})")
+    check(lib().head_lse(A=ptr(x), lda=x.stride(0), W=ptr(w), ldw=w.stride(0), rowstat=ptr(rowstat),
+                         colsum=ptr(colsum), bias=ptr(bias), target=ptr(target), out_idx=ptr(out_idx), M=M, V=V, d=d,
+                         ws=ptr(ws), ws_bytes=ws.numel() * 4, tok_lp=ptr(tok_lp), top_id=ptr(top_id),
+                         top_lp=ptr(top_lp), out_len=tok_lp.numel(), st=stream_ptr()), "head_lse")
+
+
 def shuffle_weight(w: torch.Tensor) -> torch.Tensor:
     """Pre-shuffle a decode weight [N, K] (bf16, or e4m3 bytes) into the skinny
     GEMM's MFMA fragment order: for column tile t (16 rows) and 64-B chunk c,

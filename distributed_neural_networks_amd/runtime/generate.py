@@ -110,7 +110,8 @@ def needs_prompt_ids(pipe) -> bool:
     logit constraints that read the rows' context (``no_repeat_ngram_size``, a
     bad word longer than one token)."""
     cons = getattr(pipe, "constraints", None)
-    return penalties_on(pipe) or (cons is not None and cons.needs_context)
+    return (penalties_on(pipe) or (cons is not None and cons.needs_context)
+            or bool(getattr(pipe, "prompt_logprobs", 0)))  # ... or to score the prompt's own tokens
 
 
 def _sync(dev):
@@ -167,6 +168,33 @@ def _report_logprobs(nid: str, ring: DecodeRing) -> None:
     log("LOGPROBS " + json.dumps(rec))
 
 
+def _report_prompt_logprobs(nid: str, ring: DecodeRing) -> None:
+    """One ``PROMPT_LOGPROBS {...}`` JSON line from the rank that holds the last
+    stage (config key ``prompt_logprobs``): per sequence the sum of its prompt
+    tokens' log-probabilities, their count (the first token has none) and the
+    mean negative log-likelihood; the share of positions whose most likely
+    entry is the prompt's token; the first sequence's per-token values
+    (``DNN_LOGPROBS_ALL=1``: every sequence's), position 0 as null."""
+    if ring.plp is None:
+        return
+    import os
+    mbs = ring.prompt_logprobs()
+    seqs = [(t, i, l) for mb in mbs for t, i, l in zip(mb["tok_lp"], mb["top_id"], mb["top_lp"])]
+    sums = [float(t[1:].double().sum()) for t, _, _ in seqs]
+    cnts = [int(t.numel()) - 1 for t, _, _ in seqs]
+    hit = sum(int((i[1:] == p[1:]).sum()) for mb in mbs for i, p in zip(mb["top_id"], mb["ids"]))
+
+    def per_token(t, i, l):
+        return {"tok_lp": [None] + t[1:].tolist(), "top_id": [None] + i[1:].tolist(), "top_lp": [None] + l[1:].tolist()}
+    rec = {"node": nid, "sum": sums, "tokens": cnts,
+           "mean_nll": [(-s / c if c else None) for s, c in zip(sums, cnts)],
+           "top1_share": (hit / sum(cnts) if sum(cnts) else None),
+           "seq0": per_token(*seqs[0])}
+    if os.environ.get("DNN_LOGPROBS_ALL") == "1":
+        rec["all"] = [per_token(*q) for q in seqs]
+    log("PROMPT_LOGPROBS " + json.dumps(rec))
+
+
 def _report_finish(nid: str, ring: DecodeRing) -> None:
     """One ``FINISH {...}`` JSON line from the rank that holds the last stage
     (config keys ``eos_token_id`` / ``stop_token_ids`` / ``stop_sequences``):
@@ -210,6 +238,7 @@ def run_generate_colocated(ctx, args, stages: List, device) -> int:
     pf, dec, steps = _timed_generate(ring, prompts, T, steps, device, pipe.prefill_chunk, mlens)
     _report(ctx.node_id, ring.tokens(), pf, dec, n_seq, T, steps, M, 1, lens)
     _report_logprobs(ctx.node_id, ring)
+    _report_prompt_logprobs(ctx.node_id, ring)
     _report_finish(ctx.node_id, ring)
     return 0
 
@@ -255,5 +284,6 @@ def run_generate_dist(ctx, args, stage, info, progress=None) -> int:
         nid = ctx.node_id + (f" replica {ctx.replica}" if getattr(pipe, "replicas", 1) > 1 else "")
         _report(nid, ring.tokens(), pf, dec, B * M, T, steps, M, S, lens)
     _report_logprobs(ctx.node_id, ring)  # the last rank's: nothing new travels over the back-edge
+    _report_prompt_logprobs(ctx.node_id, ring)
     _report_finish(ctx.node_id, ring)  # likewise: the padded tokens are all that travels
     return 0

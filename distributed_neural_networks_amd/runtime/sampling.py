@@ -420,3 +420,28 @@ def pick(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, seed: i
     if top_p >= 1.0 and min_p <= 0.0:
         return sample_topk_ref(logits, temperature, top_k, seed, step)
     return sample_ref(logits, temperature, top_k, top_p, min_p, seed, step)
+
+
+def prompt_logprobs_ref(logits: torch.Tensor, targets: torch.Tensor):
+    """Torch mirror of csrc/kernels/head_lse.hip on ready-made logits: for
+    every row of (M, V) logits, rounded to bf16 as the head stores them, the
+    fp64 ``log_softmax`` value of ``targets[row]`` and the most likely entry
+    (value descending, index ascending) with its value: ``(tok_lp, top_id,
+    top_lp)`` as fp32, int32, fp32 (M,).  A target outside [0, V) gives
+    (0, -1, 0): "record nothing"."""
+    if logits.dim() != 2 or targets.numel() != logits.shape[0]:
+        raise ValueError(f"prompt_logprobs: (M, V) logits and M targets expected, got {tuple(logits.shape)}, "
+                         f"{tuple(targets.shape)}")
+    M, V = logits.shape
+    lb = logits.to(torch.bfloat16).to(torch.float64)
+    lsm = lb - torch.logsumexp(lb, dim=1, keepdim=True)
+    mx = lb.max(dim=1, keepdim=True).values
+    ar = torch.arange(V, device=lb.device)[None].expand(M, V)
+    top_id = torch.where(lb == mx, ar, V).min(dim=1).values
+    tg = targets.reshape(M).to(device=lb.device, dtype=torch.int64)
+    live = (tg >= 0) & (tg < V)
+    tok = lsm.gather(1, tg.clamp(0, V - 1)[:, None])[:, 0]
+    top = lsm.gather(1, top_id[:, None])[:, 0]
+    zero = torch.zeros_like(tok)
+    return (torch.where(live, tok, zero).float(), torch.where(live, top_id, -1).to(torch.int32),
+            torch.where(live, top, zero).float())

@@ -458,6 +458,29 @@ class DecodeRing:
             for m in range(M):
                 self.stages[-1].bind_logprobs(m * B, self.lp_chosen[m], self.lp_top_ids[m], self.lp_top_lps[m])
 
+        # last stage with prompt log-probabilities (its ``prompt_logprobs`` = 1): per-microbatch histories
+        # indexed by prompt position, written by the stage's own launch in every prefill piece
+        # (``bind_prompt_logprobs``): plp_tok[m][b, p] = log P(ids[b, p] | ids[b, :p]), plp_top_id / plp_top_lp
+        # the most likely entry there; position 0 and everything from the row's length on keep (0, -1, 0)
+        self.plp = self.stages[-1] if self.last and getattr(self.stages[-1], "prompt_logprobs", 0) else None
+        self.plp_tok = self.plp_top_id = self.plp_top_lp = None
+        self.plp_len: List[object] = [0] * M  # prompt lengths of the current generation (ragged: a host (B,) tensor)
+        self.plp_ids: List[object] = [None] * M  # ... and its prompt ids, on the host
+        if self.plp is not None:
+            if n_groups > 1 and not self.forward_prompt_ids:
+                raise ValueError("a last stage with prompt_logprobs on a ring of several groups needs "
+                                 "forward_prompt_ids=True on every rank (the prompt ids live on group 0)")
+            cap = int(getattr(self.plp, "max_seq", 0) or 0)
+            if cap <= 0:
+                from ..models import model_info
+                cfg = model_info(self.plp.model).cfg
+                cap = int(getattr(cfg, "block_size", getattr(cfg, "max_seq", 1024)))
+            self.plp_tok = [torch.zeros((B, cap), dtype=torch.float32, device=dev) for _ in range(M)]
+            self.plp_top_id = [torch.full((B, cap), -1, dtype=torch.int32, device=dev) for _ in range(M)]
+            self.plp_top_lp = [torch.zeros((B, cap), dtype=torch.float32, device=dev) for _ in range(M)]
+            for m in range(M):
+                self.plp.bind_prompt_logprobs(m * B, self.plp_tok[m], self.plp_top_id[m], self.plp_top_lp[m])
+
         # last stage with stop conditions (its ``stop`` is a config.StopConfig): the per-row state lives on the
         # stage, starts at every prefill (stop_begin), forgets the discarded sample of a non-final prefill
         # piece (stop_forget) and survives the capture runs through snapshots (capture)
@@ -615,6 +638,10 @@ class DecodeRing:
                 self.lp_top_ids[m].zero_()
                 self.lp_top_lps[m].zero_()
                 self.lp_base[m], self.lp_cnt[m] = 0, 0
+            if self.plp is not None:
+                self.plp_tok[m].zero_()
+                self.plp_top_id[m].fill_(-1)
+                self.plp_top_lp[m].zero_()
         in_dt, out_dt = _act_dtype(self.stages[0]), _act_dtype(self.stages[-1])
         xin_pf = torch.empty((B * C, d), dtype=in_dt, device=self.dev) if not self.first else None
         out_pf = None
@@ -647,6 +674,12 @@ class DecodeRing:
                 self.pen.penalty_begin(m * B, ids, lens=ln)
             if self.con is not None:
                 self.con.constraint_begin(m * B, ids, lens=ln)  # the rows' context starts as their own prompt
+            if self.plp is not None:
+                self.plp.prompt_begin(m * B, ids, lens=ln)  # every piece below scores its prompt positions
+                # the host copies come from the caller where it has them: no device sync inside the prefill
+                self.plp_len[m] = (torch.as_tensor(lens[m]).reshape(-1).long().cpu() if self.first else ln.cpu().long()) \
+                    if rag else T
+                self.plp_ids[m] = prompts[m].detach().to("cpu", torch.int32) if self.first else ids.cpu()
             self._out_ready(m)
             for t0, Tc in pieces:
                 final = t0 + Tc == Tm
@@ -689,6 +722,8 @@ class DecodeRing:
                     else:
                         self._send(m)
                 self.progress()
+            if self.plp is not None:
+                self.plp.prompt_end(m * B)
         for w in pf_work:
             if w is not None:
                 w.wait()
@@ -698,6 +733,23 @@ class DecodeRing:
             self.pending = [True] * self.M  # every prompt's first token comes back over the back-edge
         self.steps_done = 0
         self._fin_i = 0
+
+    def prompt_logprobs(self) -> List[Dict[str, List[torch.Tensor]]]:
+        """Per microbatch ``{"tok_lp", "top_id", "top_lp", "ids"}``: for every sequence
+        a host tensor over its own prompt positions (``ids``: the prompt itself).  Entry p is the
+        log-probability of prompt token p given the tokens before it, and the
+        most likely entry at p with its log-probability; position 0 has no
+        entry (0, -1, 0)."""
+        if self.plp is None:
+            raise ValueError("prompt_logprobs: the last stage records none (config key 'prompt_logprobs')")
+        res = []
+        for m in range(self.M):
+            ln = self.plp_len[m]
+            lens = ln.tolist() if isinstance(ln, torch.Tensor) else [int(ln)] * self.B
+            hs = {"tok_lp": self.plp_tok[m].cpu(), "top_id": self.plp_top_id[m].cpu(), "top_lp": self.plp_top_lp[m].cpu(),
+                  "ids": self.plp_ids[m]}
+            res.append({k: [v[b, :lens[b]].clone() for b in range(self.B)] for k, v in hs.items()})
+        return res
 
     # -- decode -------------------------------------------------------------------
     def capture(self) -> None:

@@ -176,7 +176,8 @@ class TorchStage(StageCompute):
     """Golden torch module as a stage (CPU fp32 plumbing path / tests)."""
 
     def __init__(self, model: str, sd: Dict[str, torch.Tensor], start: int, end: int, first: bool, last: bool,
-                 device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0), input_dtype: str = "fp32", input_table=None):
+                 device="cpu", dtype=torch.float32, sampling=(0.0, 0, 0), input_dtype: str = "fp32", input_table=None,
+                 prompt_logprobs: int = 0):
         from ..models import build_golden_stage
         # sampling = (temperature, top_k, seed[, top_p, min_p[, repetition, presence, frequency penalty[, logprobs
         #             [, stop (config.StopConfig or None)[, constraints (config.ConstraintConfig or None)]]]]])
@@ -194,6 +195,13 @@ class TorchStage(StageCompute):
             raise ValueError(f"logprobs must be an integer in [0, {LOGPROBS_MAX_N}], got {nlp!r}")
         self.logprobs = nlp if last else 0
         self._lp_hist: Dict[int, tuple] = {}
+        # prompt log-probabilities (last stage): every prefill piece between prompt_begin and prompt_end scores
+        # its prompt positions through the mirror (runtime/sampling.py prompt_logprobs_ref)
+        if prompt_logprobs not in (0, 1):
+            raise ValueError(f"prompt_logprobs must be 0 or 1, got {prompt_logprobs!r}")
+        self.prompt_logprobs = prompt_logprobs if last else 0
+        self._plp_hist: Dict[int, tuple] = {}
+        self._plp_ids: Dict[int, tuple] = {}
         # stop conditions (last stage): the mirror's state (runtime/sampling.py stop_ref) per microbatch offset
         self.stop = sampling[9] if len(sampling) >= 10 and last else None
         self._stop_st: Dict[int, torch.Tensor] = {}
@@ -346,6 +354,42 @@ class TorchStage(StageCompute):
             raise ValueError("bind_logprobs: this stage records no log-probabilities")
         self._lp_hist[b0] = (chosen, top_ids, top_lps)
 
+    def bind_prompt_logprobs(self, b0: int, tok_lp: torch.Tensor, top_id: torch.Tensor, top_lp: torch.Tensor) -> None:
+        """The prompt histories of cache rows [b0, b0 + B), fp32, int32, fp32 (B, L)
+        (``TransformerStage.bind_prompt_logprobs``)."""
+        if not self.prompt_logprobs:
+            raise ValueError("bind_prompt_logprobs: this stage records no prompt log-probabilities")
+        self._plp_hist[b0] = (tok_lp, top_id, top_lp)
+
+    def prompt_begin(self, b0: int, ids: torch.Tensor, lens=None) -> None:
+        """A prefill of cache rows [b0, b0 + B) starts on the (B, T) prompts
+        ``ids`` (``lens``: their own lengths); until ``prompt_end`` every
+        ``step`` at these rows is a prefill piece."""
+        if b0 not in self._plp_hist:
+            raise ValueError(f"prompt_logprobs: no bind_prompt_logprobs for cache rows at {b0}")
+        B, T = ids.shape
+        ln = torch.full((B,), T, dtype=torch.int64) if lens is None else torch.as_tensor(lens).reshape(B).long()
+        self._plp_ids[b0] = [ids.long(), ln, 0]  # ... and the prompt position the next piece starts at
+
+    def prompt_end(self, b0: int) -> None:
+        self._plp_ids.pop(b0, None)
+
+    def _record_prompt(self, hid: torch.Tensor, b0: int, B: int, T: int) -> None:
+        """The next T prompt positions [t0, t0 + T) of a prefill on their hidden states (B, T, d):
+        position p predicts ``ids[b, p + 1]``, recorded at p + 1; a row's last
+        prompt position and its pads record nothing (``TransformerStage._record_prompt``)."""
+        from .sampling import prompt_logprobs_ref
+        ids, ln, t0 = self._plp_ids[b0]
+        self._plp_ids[b0][2] = t0 + T  # (the equal-length path passes step no t0: the pieces come in order)
+        p1 = torch.arange(t0 + 1, t0 + T + 1)
+        tgt = torch.where(p1[None, :] < ln[:, None], ids[:, p1.clamp(max=ids.shape[1] - 1)], -1)
+        V = model_info(self.model).cfg.vocab_size
+        tok, tid, top = prompt_logprobs_ref(self._head(hid).reshape(B * T, V).float(), tgt.reshape(B * T))
+        live = (tgt >= 0).reshape(B * T)
+        at = (torch.arange(B)[:, None].expand(B, T).reshape(-1)[live], p1[None, :].expand(B, T).reshape(-1)[live])
+        for hist, v in zip(self._plp_hist[b0], (tok, tid, top)):
+            hist[at] = v[live]
+
     def _hidden(self, h, kv, p: int):
         """The module's blocks (and embedding) without its head: (B, T, d)."""
         return self.module(h, kv, p, head=False)
@@ -388,7 +432,10 @@ class TorchStage(StageCompute):
             h = x.view(B, T, cfg.n_embd).to(self.dtype)
         if lens is not None and self.last:
             from .sampling import ragged_last_rows_ref
-            hid = self._hidden(h, kv, p).reshape(B * T, cfg.n_embd)
+            hid = self._hidden(h, kv, p)
+            if b0 in self._plp_ids:
+                self._record_prompt(hid, b0, B, T)
+            hid = hid.reshape(B * T, cfg.n_embd)
             keep = getattr(self, "_h_last", None)
             if keep is None:
                 keep = self._h_last = {}
@@ -400,6 +447,8 @@ class TorchStage(StageCompute):
             y = self.module(h, kv, p)
         elif uniform:
             hid = self._hidden(h, kv, p)
+            if b0 in self._plp_ids:
+                self._record_prompt(hid, b0, B, T)
             y = self._head(hid[:, -1:, :] if last_only else hid)
         else:
             hid = torch.cat([self._hidden(h[b:b + 1], [(k[b:b + 1], v[b:b + 1]) for k, v in kv], ps[b])

@@ -98,7 +98,8 @@ class TransformerStage(StageCompute):
                  kv_dtype: str = "bf16", kv_scale: str = "calibrated", fp8_prefill: str = "e4m3",
                  top_p: float = 1.0, min_p: float = 0.0, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprobs: int = 0, stop=None,
-                 constraints=None, w4: bool = False, mxfp4_prefill: str = "bf16", mxfp4_head: str = "bf16"):
+                 constraints=None, w4: bool = False, mxfp4_prefill: str = "bf16", mxfp4_head: str = "bf16",
+                 prompt_logprobs: int = 0):
         info = model_info(model)
         if w4 and fp8:
             raise ValueError("w4 (MXFP4 weights) and fp8 weights exclude each other")
@@ -162,6 +163,13 @@ class TransformerStage(StageCompute):
         if not isinstance(logprobs, int) or isinstance(logprobs, bool) or not 0 <= logprobs <= T_.LOGPROBS_MAX_N:
             raise ValueError(f"logprobs must be an integer in [0, {T_.LOGPROBS_MAX_N}], got {logprobs!r}")
         self.logprobs = logprobs if last else 0
+        # prompt log-probabilities (last stage): 1 = every prefill piece scores its prompt positions with the
+        # fused head + log-sum-exp launch (csrc/kernels/head_lse.hip), which reads the bf16 folded head
+        if prompt_logprobs not in (0, 1):
+            raise ValueError(f"prompt_logprobs must be 0 or 1, got {prompt_logprobs!r}")
+        if prompt_logprobs and last and (fp8 or mxfp4_head == "mxfp4"):
+            raise ValueError("prompt_logprobs reads a bf16 vocabulary head: not with fp8 weights or an MXFP4 head")
+        self.prompt_logprobs = prompt_logprobs if last else 0
         # stop conditions (last stage; config.StopConfig or None): per-row device state updated by a launch of
         # its own behind the argmax / sampler, and with min_new_tokens a suppression launch in front of it
         # (csrc/kernels/stop.hip); None = nothing allocated, nothing launched
@@ -499,6 +507,12 @@ class TransformerStage(StageCompute):
         if self.logprobs:
             self.lp_ws = T_.logprobs_workspace(self.max_batch, self.V, self.logprobs, dev)
 
+        # prompt log-probabilities: histories bound per microbatch (bind_prompt_logprobs), the prompt ids of a
+        # running prefill (prompt_begin .. prompt_end), and the launch's buffers, allocated by its first use
+        self._plp_hist: Dict[int, tuple] = {}
+        self._plp_ids: Dict[int, tuple] = {}
+        self.plp_ws = self.plp_stats = None
+
         # stop conditions: g, the finish record and the window of every KV row
         self.stop_state = T_.stop_state(self.max_batch, dev) if self.stop is not None else None
 
@@ -611,6 +625,62 @@ class TransformerStage(StageCompute):
         if b0 < 0 or b0 + chosen.shape[0] > self.max_batch:
             raise ValueError(f"bind_logprobs: rows [{b0}, {b0 + chosen.shape[0]}) outside the {self.max_batch} rows")
         self._lp_hist[b0] = (chosen, top_ids, top_lps)
+
+    def bind_prompt_logprobs(self, b0: int, tok_lp: torch.Tensor, top_id: torch.Tensor, top_lp: torch.Tensor) -> None:
+        """The prompt histories of cache rows [b0, b0 + B): ``tok_lp`` fp32,
+        ``top_id`` int32 and ``top_lp`` fp32, all (B, L), on this device.  Between
+        ``prompt_begin`` and ``prompt_end`` every prefill piece at these rows
+        writes, at prompt position p + 1, the log-probability of the prompt's
+        token there given the tokens before it, and the most likely entry."""
+        if not self.prompt_logprobs:
+            raise ValueError("bind_prompt_logprobs: this stage records no prompt log-probabilities")
+        ok = (tok_lp.dtype == torch.float32 and top_id.dtype == torch.int32 and top_lp.dtype == torch.float32
+              and tok_lp.dim() == 2 and top_id.shape == tok_lp.shape == top_lp.shape
+              and all(t.is_contiguous() and t.device == self.device for t in (tok_lp, top_id, top_lp)))
+        if not ok:
+            raise ValueError(f"bind_prompt_logprobs: fp32, int32 and fp32 (B, L), contiguous on {self.device}, expected")
+        if b0 < 0 or b0 + tok_lp.shape[0] > self.max_batch:
+            raise ValueError(f"bind_prompt_logprobs: rows [{b0}, {b0 + tok_lp.shape[0]}) outside the {self.max_batch} rows")
+        self._plp_hist[b0] = (tok_lp, top_id, top_lp)
+
+    def prompt_begin(self, b0: int, ids: torch.Tensor, lens: Optional[torch.Tensor] = None) -> None:
+        """A prefill of cache rows [b0, b0 + B) starts: ``ids`` (B, T) int32 are
+        its prompts (``lens``: their own lengths, right-padded).  Until
+        ``prompt_end`` every ``step`` at these rows is a prefill piece."""
+        if b0 not in self._plp_hist:
+            raise ValueError(f"prompt_logprobs: no bind_prompt_logprobs for cache rows at {b0}")
+        ids = ids.to(device=self.device, dtype=torch.int32)
+        B, T = ids.shape
+        if T > self._plp_hist[b0][0].shape[1]:
+            raise ValueError(f"prompt_logprobs: the histories hold {self._plp_hist[b0][0].shape[1]} positions, got {T}")
+        ln = (torch.full((B,), T, dtype=torch.int64, device=self.device) if lens is None
+              else lens.to(device=self.device, dtype=torch.int64).reshape(B))
+        self._plp_ids[b0] = [ids.long(), ln, 0]  # ... and the prompt position the next piece starts at
+
+    def prompt_end(self, b0: int) -> None:
+        self._plp_ids.pop(b0, None)
+
+    def _record_prompt(self, h: torch.Tensor, b0: int, B: int, T: int) -> None:
+        """The prompt log-probability launch of the prefill's next piece [t0, t0 + T) on
+        its B * T hidden rows ``h`` (row b T + t): position p = t0 + t predicts
+        ``ids[b, p + 1]``, recorded at p + 1; the row's last prompt position
+        (its successor is generated: ``logprobs`` has it) and every pad have
+        target -1 and write nothing."""
+        ids, ln, t0 = self._plp_ids[b0]
+        self._plp_ids[b0][2] = t0 + T  # (the equal-length path passes step no t0: the pieces come in order)
+        tok_lp, top_id, top_lp = self._plp_hist[b0]
+        L, M = tok_lp.shape[1], B * T
+        p1 = torch.arange(t0 + 1, t0 + T + 1, device=self.device)
+        live = p1[None, :] < ln[:, None]
+        tgt = torch.where(live, ids[:, p1.clamp(max=ids.shape[1] - 1)], -1).to(torch.int32).reshape(M).contiguous()
+        oidx = (torch.arange(B, device=self.device)[:, None] * L + p1[None, :]).to(torch.int32).reshape(M).contiguous()
+        if self.plp_stats is None or self.plp_stats.numel() < 2 * M:
+            self.plp_stats = torch.empty((2 * M,), dtype=torch.float32, device=self.device)
+        need = G_.head_lse_workspace(M, self.V, "meta").numel()
+        if self.plp_ws is None or self.plp_ws.numel() < need:
+            self.plp_ws = torch.empty((need,), dtype=torch.float32, device=self.device)
+        G_.head_lse(h, self.w_head, tgt, oidx, tok_lp.view(-1), top_id.view(-1), top_lp.view(-1), self.plp_ws,
+                    stats=self.plp_stats)
 
     def _record_logprobs(self, logits, tokens, b0: int, rows: int, T: int, pos, advanced: bool) -> None:
         """The log-probability launch of a ``last_only`` step: ``tokens`` is what
@@ -862,6 +932,8 @@ class TransformerStage(StageCompute):
                 out.view(ntok, d).copy_(h)
                 return out
             return h
+        if self.prompt_logprobs and b0 in self._plp_ids:
+            self._record_prompt(h, b0, B, T)  # in front of the tail, which leaves h as it is
         if lens is not None:
             # a piece of a ragged prefill: nothing is sampled here; each row whose own last prompt position
             # lies in [t0, t0 + T) leaves its hidden state for ragged_first_token
@@ -1059,7 +1131,7 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                        kv_scale: str = "calibrated", fp8_prefill: str = "e4m3", top_p: float = 1.0,
                        min_p: float = 0.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                        frequency_penalty: float = 0.0, logprobs: int = 0, stop=None, constraints=None,
-                       mxfp4_prefill: str = "bf16", mxfp4_head: str = "bf16"):
+                       mxfp4_prefill: str = "bf16", mxfp4_head: str = "bf16", prompt_logprobs: int = 0):
     fp8 = dtype in ("fp8", "float8_e4m3fn", "fp8_e4m3")
     w4 = dtype == "mxfp4"
     info = model_info(model)
@@ -1069,7 +1141,7 @@ def build_device_stage(model: str, sd, start: int, end: int, first: bool, last: 
                             top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
                             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                             logprobs=logprobs, stop=stop, constraints=constraints, w4=w4,
-                            mxfp4_prefill=mxfp4_prefill, mxfp4_head=mxfp4_head)
+                            mxfp4_prefill=mxfp4_prefill, mxfp4_head=mxfp4_head, prompt_logprobs=prompt_logprobs)
 
 
 # ---------------------------------------------------------------------- smoke / golden check
